@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput benchmark of the reverse-SDE sampling hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch per GPU: 16 synthetic 4-s utterances
@@ -10,12 +10,17 @@ One "step" = one pass of the hot path over one batch per GPU: 16 synthetic 4-s u
 -> iSTFT.  This is BASELINE.json configs[1] (configs[2] = the same per GPU on 8 GPUs: utterances are
 sharded over ranks, no data-path collective -> "scaling": "weak").
 
-Rank 0 prints ONE JSON line with the contract fields plus
-  roofline     — the dominant kernel (implicit-GEMM 3x3 conv, bf16 MFMA): algorithmic FLOPs per
-                 launch / average launch duration, measured with HIP events on the launch stream
-                 (storm_program_run_timed) over profiled score evaluations of the same workload;
-  cpu_baseline — the CPU oracle (oracle/, "port") timed on this host on a bounded sample
-                 (one score evaluation of one utterance), extrapolated to utterances/s.
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs with
+--dump-outputs and prints ONE JSON line (rank 0) with the contract fields.  --full adds, after the
+timed region (each can still be switched off by its --no-* option):
+  from_host     — the same steps again from pinned host wavs (H2D + sampler + D2H);
+  roofline      — the dominant kernel (implicit-GEMM 3x3 conv, bf16 MFMA): algorithmic FLOPs per
+                  launch / average launch duration, measured with HIP events on the launch stream
+                  (storm_program_run_timed) over profiled score evaluations of the same workload,
+                  with roofline_hbm, socket power and (configs[1]) PMC traffic passes beside it;
+  other_configs — the other BASELINE.json configurations, each timed on its own (configs[1] only);
+  cpu_baseline  — the CPU oracle (oracle/, "port") timed on this host on a bounded sample
+                  (one score evaluation of one utterance), extrapolated to utterances/s.
 """
 import argparse
 import ctypes as C
@@ -52,6 +57,12 @@ def parse():
     p.add_argument("--corrector-steps", type=int, default=1)
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     p.add_argument("--backbone", default="ncsnpp")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline region also measure from_host, roofline / roofline_hbm (+ power, PMC traffic), other_configs and "
+                        "cpu_baseline (a plain run times the headline steps only)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step returned (the enhanced wavs, the evaluations per utterance) as DIR/<name>.npy, "
+                        "float32 / float64, at most 64 MB in all (a seeded sample of a larger output)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-roofline", action="store_true")
     p.add_argument("--profile-nfe", type=int, default=2, help="score evaluations profiled with per-op HIP events")
@@ -69,7 +80,7 @@ def parse():
     p.add_argument("--no-h2d", action="store_true",
                    help="skip the second timed pass from HOST wavs (pinned: H2D of the batch, the sampler, D2H of the result - SURVEY 8(d)), "
                         "which is reported as `from_host` beside `value`, never as it")
-    p.add_argument("--include-h2d", action="store_true", help="(accepted for old command lines: the from-host pass is now the default)")
+    p.add_argument("--include-h2d", action="store_true", help="(accepted for old command lines: the from-host pass is part of --full)")
     p.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                    help="HIP-graph replay of the score evaluations (storm_ncsnpp_set_graph): auto = the library's rule (today: eager at every batch size, profiles/r05a_*)")
     p.add_argument("--no-other-configs", action="store_true",
@@ -83,7 +94,34 @@ def parse():
                         "untimed repetition of the same step instead)")
     p.add_argument("--selftest-cpu", action="store_true",
                    help="(tests) run the launch / sharding / timing skeleton with a stand-in step on CPU ranks (gloo)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.ops_json and not args.full:
+        p.error("--ops-json writes the per-op table of the roofline pass: it needs --full")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, suffix=""):
+    """Write {name: tensor / number} as outdir/<name><suffix>.npy (float32, or float64 for float64 data and plain numbers).  When the
+    whole set exceeds DUMP_LIMIT_BYTES, each array keeps a fixed, seeded sample of its flattened elements (same positions every run
+    at the same shapes), stored beside it as <name><suffix>_index.npy (float64 positions into the flattened array)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    whole = sum(a.nbytes for a in host.values())
+    keep = 1.0 if whole <= DUMP_LIMIT_BYTES else DUMP_LIMIT_BYTES / (whole + sum(8 * a.size for a in host.values()))   # (values + indices)
+    for name, a in host.items():
+        if keep < 1.0 and a.size > 1:
+            n = max(1, int(a.size * keep))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            np.save(os.path.join(outdir, f"{name}{suffix}_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a)
 
 
 def randomize(model, seed):
@@ -435,7 +473,7 @@ def main():
         # one stream (kernels of concurrent queues corrupt each other on this platform, profiles/r06_concurrent_repro.txt); the micro-batches
         # share LAUNCHES instead: ScoreModel.enhance_stream runs their samplers in lockstep around one grouped network call per step
         outs, n_ = model.enhance_stream(batches, grouped=not args.no_group, seed=1000 * rank + 100 * i, return_nfe=True, width=args.width, **skw)
-        return outs[-1], n_                                 # mean score evaluations per utterance
+        return outs, n_                                     # every micro-batch's wavs, mean score evaluations per utterance
 
     # socket power: by default NOT sampled inside the timed region (the sampler spawns rocm-smi every 0.2 s on rank 0's host cores and
     # would perturb that rank only); one more repetition of the same step is sampled after it, on a one-rank run, where rocm-smi's
@@ -443,10 +481,15 @@ def main():
     with PowerSampler(enabled=args.power and rank == 0 and world == 1) as power:
         elapsed, per_rank, (out, nfe) = D.timed_steps(step, args.steps, args.warmup, sync=torch.cuda.synchronize, single_rank_group=args.dist_world1)
     power = power.summary() if rank == 0 else None
-    assert torch.isfinite(out).all(), "non-finite output"
+    outs = out if args.stream else [out]
+    assert all(torch.isfinite(o).all() for o in outs), "non-finite output"
+    if args.dump_outputs:                                   # what the last timed step returned, before anything else runs on the model
+        arrays = {f"enhanced_wav_mb{k}": o for k, o in enumerate(outs)} if args.stream else {"enhanced_wav": out}
+        arrays["nfe_per_utterance"] = nfe
+        dump_outputs(args.dump_outputs, arrays, suffix=f"_rank{rank}" if world > 1 else "")
     value = units * world * args.steps / elapsed
     h2d = None
-    if not args.no_h2d and not args.stream:                 # the same step from host memory: H2D + sampler + D2H inside the timed region
+    if args.full and not args.no_h2d and not args.stream:   # the same step from host memory: H2D + sampler + D2H inside the timed region
         wav_host = wav.cpu().pin_memory()
         out_host = torch.empty(out.shape, dtype=out.dtype).pin_memory()
 
@@ -497,7 +540,7 @@ def main():
         dist.destroy_process_group()
         dist = None
 
-    if rank == 0 and world == 1 and not args.power and not args.no_roofline and not args.stream:
+    if args.full and rank == 0 and world == 1 and not args.power and not args.no_roofline and not args.stream:
         with PowerSampler(enabled=True) as ps:               # untimed repetitions of the same step, sampled
             for i in range(2):
                 step(args.warmup + args.steps + i)
@@ -505,7 +548,7 @@ def main():
         power = ps.summary()
         if power is not None:
             power["sampled"] = "two untimed repetitions of the step after the timed region"
-    if rank == 0 and not args.no_roofline and not args.stream:
+    if args.full and rank == 0 and not args.no_roofline and not args.stream:
         Y, _, _ = model._prepare(wav)
         rows = profile_ops(model.dnn, Y, args.profile_nfe)
         groups = {}                                        # 3x3 convolutions on the matrix cores, by the kernel the launcher picked
@@ -614,13 +657,13 @@ def main():
             with open(args.ops_json, "w") as f:
                 json.dump(rows, f, indent=0)
 
-    if rank == 0 and world == 1 and not args.no_other_configs and not args.stream and cfg_name == "configs[1]":
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs and not args.stream and cfg_name == "configs[1]":
         t0 = time.perf_counter()
         result["other_configs"] = other_configs(model, dev, torch.cuda.synchronize)
         result["other_configs"]["seconds_spent"] = round(time.perf_counter() - t0, 1)
         model.set_precision(args.precision)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         dt, times, cores = cpu_baseline(args.backbone, args.seconds)
         result["cpu_baseline"] = {
             "value": 1.0 / (dt * nfe), "unit": "utterances/s", "cores": cores, "kind": "port",

@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -143,11 +144,12 @@ def test_numa_pinning_helpers(tmp_path):
 
 
 @pytest.mark.gpu
-def test_bench_under_the_driver_launch_line_with_an_rccl_group_of_one():
+def test_bench_under_the_driver_launch_line_with_an_rccl_group_of_one(tmp_path):
     """The driver starts the multi-GPU bench as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py --gpus N ...`.  On the one GPU a test box has, run exactly that line with N = 1 and --dist-world1, so that
     bench.py's own init_process_group("nccl", device_id=...), the barrier / all_gather_object fences of distributed.timed_steps and the
-    leave-together barrier execute on ROCm / RCCL before the driver runs them at N = 8; and the --include-h2d variant of the step."""
+    leave-together barrier execute on ROCm / RCCL before the driver runs them at N = 8; and the --include-h2d variant of the step (--full)
+    and --dump-outputs."""
     import json
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
@@ -155,7 +157,7 @@ def test_bench_under_the_driver_launch_line_with_an_rccl_group_of_one():
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29577", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--N", "2", "--batch", "2",
-           "--seconds", "1", "--no-cpu-baseline", "--no-roofline", "--dist-world1", "--include-h2d"]
+           "--seconds", "1", "--full", "--no-cpu-baseline", "--no-roofline", "--dist-world1", "--include-h2d", "--dump-outputs", str(tmp_path)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-2500:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -164,3 +166,28 @@ def test_bench_under_the_driver_launch_line_with_an_rccl_group_of_one():
     assert r["n_gpus"] == 1 and r["process_group"] == {"backend": "nccl", "world_size": 1}
     assert r["config"]["nfe_per_utterance"] == 4 and len(r["per_rank_s"]) == 1
     assert r["from_host"]["value_from_host_wavs"] > 0 and r["from_host"]["bytes_per_step"] == 2 * 2 * 16000 * 4
+    # --dump-outputs: the last timed step's enhanced wavs and evaluation count, as the caller of the step received them
+    wav = np.load(tmp_path / "enhanced_wav.npy")
+    assert wav.dtype == np.float32 and wav.shape == (2, 16000) and np.isfinite(wav).all() and np.abs(wav).max() > 0
+    assert float(np.load(tmp_path / "nfe_per_utterance.npy")) == 4
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays under the size limit are written whole (float32 / float64); over it, every array keeps the same
+    seeded sample of its elements in every run, with the sampled positions beside it."""
+    import bench
+    x = torch.randn(4, 1000, generator=torch.Generator().manual_seed(0))
+    bench.dump_outputs(str(tmp_path / "whole"), {"wav": x, "nfe": 60})
+    assert np.load(tmp_path / "whole" / "wav.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "whole" / "wav.npy"), x.numpy())
+    nfe = np.load(tmp_path / "whole" / "nfe.npy")
+    assert nfe.dtype == np.float64 and float(nfe) == 60
+    assert not (tmp_path / "whole" / "wav_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 6000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"wav": x, "nfe": 60}, suffix="_rank1")
+    a, ia = np.load(tmp_path / "a" / "wav_rank1.npy"), np.load(tmp_path / "a" / "wav_rank1_index.npy")
+    assert a.nbytes + ia.nbytes <= 6000 and 0 < a.size < x.numel()
+    assert np.array_equal(a, x.numpy().reshape(-1)[ia.astype(np.int64)])
+    assert np.array_equal(a, np.load(tmp_path / "b" / "wav_rank1.npy"))
+    assert float(np.load(tmp_path / "a" / "nfe_rank1.npy")) == 60
