@@ -43,7 +43,7 @@ const char* storm_last_error(void);
  * storm_conv_args (memset) before filling it: every optional pointer is "absent" as NULL. */
 #define STORM_ABI_VERSION 2
 int storm_abi_version(void);
-long long storm_abi_struct_bytes(int which);   /* 0: storm_conv_args, 1: storm_op, 2: storm_conv_seg, 3: storm_ncsnpp_config */
+long long storm_abi_struct_bytes(int which);   /* 0: storm_conv_args, 1: storm_op, 2: storm_conv_seg, 3: storm_ncsnpp_config, 4: storm_ncsnpp_config_ex */
 /* Test / tool hook, not part of the drop-in surface: the launchers' A/B switches (forced kernel family, pretend-small device for
  * persistent tile walks, ...) are a table filled once from the environment variables of the same names when the library is
  * first used; these two calls read / change an entry afterwards (names: STORM_CONV_VARIANT, STORM_CONV_PIPE128,
@@ -191,7 +191,9 @@ int storm_gn_finalize(const float* part_a, int Ca, int tiles_a, const float* par
 int storm_gn_finalize_ss(const float* part_a, int Ca, int tiles_a, const float* part_b, int Cb, int tiles_b,
                          int B, int groups, long long count, const float* gamma, const float* beta, float eps,
                          double* stats, float* ss, storm_stream_t s);
-/* resample: 0 none, 1 FIR up x2, 2 FIR down x2.  out_act gets act(GN(x)) (resampled),
+/* resample: 0 none, 1 FIR up x2, 2 FIR down x2; the non-FIR members of a network built with fir=False (naive_upsample_2d /
+ * naive_downsample_2d in ResnetBlockBigGANpp.forward, layerspp.py:246-258; up_or_down_sampling.py:164-178): 3 nearest up x2,
+ * 4 2x2 mean down (mean taken in fp32, rounded once).  out_act gets act(GN(x)) (resampled),
  * out_raw (may be NULL; required non-NULL only if wanted) gets the resampled raw concat. */
 int storm_gn_apply(const void* xa, int Ca, const void* xb, int Cb, int B, int H, int W,
                    int groups, const double* stats, const float* gamma, const float* beta,
@@ -257,6 +259,16 @@ int storm_output_head(const void* pyr, const float* t /* NULL: no division */, c
 int storm_input_pyramid(const float* const* cplx_in /* host array of n_in device ptrs, or NULL */, int n_in,
                         void* const* levels /* host array of n_levels device ptrs */, int n_levels, int B, int F, int T,
                         int dtype, storm_stream_t s);
+/* The same with the options of the reference constructor: mean != 0 = the non-FIR pyramid of fir=False, levels[k] = the 2x2 mean of
+ * levels[k - 1] (pyramid_downsample = Downsample(fir=False, with_conv=False) -> F.avg_pool2d(x, 2), layerspp.py:151-156); centered != 0 =
+ * the inputs are packed as they are, without the 2x - 1 of ncsnpp.py:325-327.  storm_input_pyramid is this call with (0, 0).          */
+int storm_input_pyramid_ex(const float* const* cplx_in, int n_in, void* const* levels, int n_levels, int B, int F, int T, int mean,
+                           int centered, int dtype, storm_stream_t s);
+/* Combine(method='cat') (layerspp.py:44-59; progressive_combine='cat', ncsnpp.py:204-207): out NHWC [npix][2 C] =
+ * cat([conv1x1(x) + bias, h], channels) in one pass - x: the 8-channel input-pyramid level [npix][8], w: its packed 1x1 weight
+ * [C rows][CinP] (storm_pack_conv_weight), h: [npix][C].  The convolution lands in the channel slice [0, C), h is copied to [C, 2 C). */
+int storm_combine_cat(const void* x, const void* w, int CinP, const float* bias, const void* h, void* out, long long npix, int C,
+                      int dtype, storm_stream_t s);
 /* The progressive output pyramid and the head in ONE launch: p_{L-1} = ph[L-1]; p_k = up2(p_{k+1}) + ph[k] (exactly storm_fir_up2 with
  * its add operand, every level rounded to the storage type); out = storm_output_head(p_0, ...).  ph[k]: NHWC [B][F >> k][T >> k][8], the
  * outputs of the pyramid's 3x3 convolutions, finest first, n_levels <= 8.  Replaces pyramid_upsample + "pyramid = pyramid + pyramid_h"
@@ -396,8 +408,9 @@ enum {
     STORM_OP_CONV = 4, STORM_OP_GN_STATS = 5, STORM_OP_GN_APPLY = 6, STORM_OP_FIR_UP = 7,
     STORM_OP_FIR_DOWN = 8, STORM_OP_SOFTMAX = 9, STORM_OP_OUTPUT_HEAD = 10, STORM_OP_GN_FINALIZE = 11,
     STORM_OP_ATTENTION = 12,
-    STORM_OP_INPUT_PYRAMID = 13,    /* p[0..2] complex inputs (or none: level 0 is read), p[3..6] levels; i = n_in, B, F, T, n_levels */
-    STORM_OP_OUTPUT_PYRAMID = 14    /* p[0..7] ph (finest first), p[8] t, p[9] W, p[10] bias, p[11] out; i = cin, B, F, T, negate, n_levels */
+    STORM_OP_INPUT_PYRAMID = 13,    /* p[0..2] complex inputs (or none: level 0 is read), p[3..6] levels; i = n_in, B, F, T, n_levels, mean, centered */
+    STORM_OP_OUTPUT_PYRAMID = 14,   /* p[0..7] ph (finest first), p[8] t, p[9] W, p[10] bias, p[11] out; i = cin, B, F, T, negate, n_levels */
+    STORM_OP_COMBINE_CAT = 15       /* p[0] x, p[1] w, p[2] bias, p[3] h, p[4] out; i = npix, C, CinP (storm_combine_cat) */
 };
 #define STORM_OP_NPTR 13
 #define STORM_OP_NINT 24
@@ -426,7 +439,8 @@ const char* storm_program_kernel_name(const storm_op* ops, int k, int dtype);
  * state_dict tensors and evaluates the score with one call; the Python class storm_amd.backbones.NCSNpp is a thin caller).
  * Replaces NCSNpp.__init__ / load_state_dict (ncsnpp.py:38-273) and NCSNpp.forward (ncsnpp.py:281-450) for the
  * configuration family of the StoRM hot path (BigGAN blocks, FIR resampling, output_skip / input_skip pyramids, Fourier
- * time embedding, swish).
+ * time embedding, swish); the _ex forms below take the constructor's other options (fir=False, skip_rescale=False, progressive /
+ * progressive_input = 'none', progressive_combine='cat', centered, conditional, scale_by_sigma) and say what stays refused and why.
  * ------------------------------------------------------------------------------------------ */
 typedef struct storm_ncsnpp_config {
     int nf;                     /* base width (128)                                                  */
@@ -440,6 +454,34 @@ typedef struct storm_ncsnpp_config {
     int discriminative;         /* predictive denoiser: 2 channels, no time conditioning, no 1/t       */
 } storm_ncsnpp_config;
 typedef struct storm_ncsnpp storm_ncsnpp;
+/* The extended description: the graph-shaping options of the reference constructor (ncsnpp.py:40-147) beyond the StoRM default set.
+ * struct_size = sizeof(storm_ncsnpp_config_ex) as the caller compiled it (another size: STORM_ERR_INVALID, nothing is read past it).
+ * STORM_NCSNPP_CONFIG_EX_DEFAULTS fills the options with the reference's defaults - with them every _ex entry point below is its plain
+ * namesake.  Still refused (STORM_ERR_INVALID at the Python surface: NotImplementedError): resblock_type='ddpm' and progressive /
+ * progressive_input = 'residual' (FIR fused into a strided / transposed 3x3 convolution: a kernel family of its own), nonlinearity other
+ * than swish (SiLU is fused into the convolutions' operand rewrite), fir_kernel other than [1,3,3,1], spatial_channels other than 1,
+ * embedding_type='positional' (the reference's own forward reads self.sigmas, which NCSNpp never defines: ncsnpp.py:304-308), and
+ * fir=False together with progressive='output_skip' (the reference itself fails there: layerspp.py:117 passes 'nearest' as scale_factor). */
+typedef struct storm_ncsnpp_config_ex {
+    int struct_size;
+    int nf, n_levels, ch_mult[8], num_res_blocks, n_attn, attn_resolutions[4], image_size, input_channels, discriminative;   /* as above */
+    int fir;                    /* 1: FIR [1,3,3,1] resampling; 0: nearest x2 / 2x2 mean (layerspp.py:246-258, 151-156); needs progressive == 0 */
+    int skip_rescale;           /* 1: (x + h) / sqrt(2) after the residual adds; 0: x + h (layerspp.py:88-91, 271-274)            */
+    int progressive;            /* 1: 'output_skip'; 0: 'none' - head = GroupNorm, act, conv3x3 (ncsnpp.py:258-263, 430-436)       */
+    int progressive_input;      /* 1: 'input_skip'; 0: 'none' - no input pyramid, no Combine modules                             */
+    int combine_cat;            /* 0: Combine 'sum'; 1: 'cat' - the following widths double (ncsnpp.py:204-207)                   */
+    int centered;               /* 1: no 2x - 1 at the input (ncsnpp.py:325-327)                                                 */
+    int conditional;            /* 0: no time embedding into the blocks (ncsnpp.py:317-323); forced 0 when discriminative          */
+    int scale_by_sigma;         /* 0: no division by t at the head (ncsnpp.py:438-440); forced 0 when discriminative              */
+} storm_ncsnpp_config_ex;
+#define STORM_NCSNPP_CONFIG_EX_DEFAULTS(c) do { (c)->struct_size = (int)sizeof(storm_ncsnpp_config_ex); (c)->fir = 1; (c)->skip_rescale = 1; \
+    (c)->progressive = 1; (c)->progressive_input = 1; (c)->combine_cat = 0; (c)->centered = 0; (c)->conditional = 1; (c)->scale_by_sigma = 1; } while (0)
+/* NCSNpp.__init__ / load_state_dict / forward (ncsnpp.py:38-273, 281-450) for every accepted option set: */
+int storm_ncsnpp_num_tensors_ex(const storm_ncsnpp_config_ex* cfg);
+int storm_ncsnpp_tensor_info_ex(const storm_ncsnpp_config_ex* cfg, int i, char* name, int name_len, int* ndim, long long* shape4);
+long long storm_ncsnpp_arena_bytes_ex(const storm_ncsnpp_config_ex* cfg, int dtype);
+int storm_ncsnpp_create_ex(const storm_ncsnpp_config_ex* cfg, const void* const* weights, int n_weights, int dtype, void* arena,
+                           storm_stream_t s, storm_ncsnpp** out);
 
 /* the reference state_dict of this configuration: count, then (name, shape) of tensor i in the reference's order */
 int storm_ncsnpp_num_tensors(const storm_ncsnpp_config* cfg);

@@ -48,6 +48,12 @@ class NcsnppConfig(C.Structure):
                 ("attn_resolutions", C.c_int * 4), ("image_size", C.c_int), ("input_channels", C.c_int), ("discriminative", C.c_int)]
 
 
+class NcsnppConfigEx(C.Structure):
+    """storm_ncsnpp_config_ex: struct_size, the fields of NcsnppConfig, then the constructor options"""
+    _fields_ = [("struct_size", C.c_int)] + NcsnppConfig._fields_ + [(n, C.c_int) for n in (
+        "fir", "skip_rescale", "progressive", "progressive_input", "combine_cat", "centered", "conditional", "scale_by_sigma")]
+
+
 class Ouve(C.Structure):
     _fields_ = [("theta", C.c_float), ("sigma_min", C.c_float), ("sigma_max", C.c_float), ("N", C.c_int)]
 
@@ -97,6 +103,8 @@ _SIGNATURES = {
     "storm_dense": ([_vp, _vp, _vp, _vp, _i, _i, _i, _vp], C.c_int),
     "storm_output_head": ([_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp], C.c_int),
     "storm_input_pyramid": ([C.POINTER(_vp), _i, C.POINTER(_vp), _i, _i, _i, _i, _i, _vp], C.c_int),
+    "storm_input_pyramid_ex": ([C.POINTER(_vp), _i, C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i, _vp], C.c_int),
+    "storm_combine_cat": ([_vp, _vp, _i, _vp, _vp, _vp, _ll, _i, _i, _vp], C.c_int),
     "storm_output_pyramid": ([C.POINTER(_vp), _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp], C.c_int),
     "storm_ouve_prior": ([_vp, _vp, _vp, _i, _ll, Ouve, _u64, _u64, _vp], C.c_int),
     "storm_ouve_ald_step": ([_vp, _vp, _vp, _vp, _vp, _i, _ll, Ouve, _f, _u64, _u64, _vp], C.c_int),
@@ -124,6 +132,10 @@ _SIGNATURES = {
     "storm_ncsnpp_tensor_info": ([C.POINTER(NcsnppConfig), _i, C.c_char_p, _i, C.POINTER(C.c_int), C.POINTER(C.c_longlong)], C.c_int),
     "storm_ncsnpp_arena_bytes": ([C.POINTER(NcsnppConfig), _i], C.c_longlong),
     "storm_ncsnpp_create": ([C.POINTER(NcsnppConfig), C.POINTER(_vp), _i, _i, _vp, _vp, C.POINTER(_vp)], C.c_int),
+    "storm_ncsnpp_num_tensors_ex": ([C.POINTER(NcsnppConfigEx)], C.c_int),
+    "storm_ncsnpp_tensor_info_ex": ([C.POINTER(NcsnppConfigEx), _i, C.c_char_p, _i, C.POINTER(C.c_int), C.POINTER(C.c_longlong)], C.c_int),
+    "storm_ncsnpp_arena_bytes_ex": ([C.POINTER(NcsnppConfigEx), _i], C.c_longlong),
+    "storm_ncsnpp_create_ex": ([C.POINTER(NcsnppConfigEx), C.POINTER(_vp), _i, _i, _vp, _vp, C.POINTER(_vp)], C.c_int),
     "storm_ncsnpp_destroy": ([_vp], None),
     "storm_ncsnpp_set_fusion": ([_vp, _i, _i, _i], C.c_int),
     "storm_ncsnpp_set_graph": ([_vp, _i], C.c_int),
@@ -156,7 +168,7 @@ def _bind(path, hold_gil=False):
     # the structures above mirror include/storm_hip.h by hand: refuse a library built from another header
     if lib.storm_abi_version() != ABI_VERSION:
         raise StormError(f"{path}: ABI version {lib.storm_abi_version()}, this binding is written for {ABI_VERSION}")
-    for which, cls in ((0, ConvArgs), (1, Op), (2, ConvSeg), (3, NcsnppConfig)):
+    for which, cls in ((0, ConvArgs), (1, Op), (2, ConvSeg), (3, NcsnppConfig), (4, NcsnppConfigEx)):
         if lib.storm_abi_struct_bytes(which) != C.sizeof(cls):
             raise StormError(f"{path}: sizeof({cls.__name__}) = {C.sizeof(cls)} here, {lib.storm_abi_struct_bytes(which)} in the library")
     return lib

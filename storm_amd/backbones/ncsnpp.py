@@ -104,23 +104,35 @@ class NCSNpp(nn.Module):
                  progressive_combine="sum", init_scale=0.0, fourier_scale=16, image_size=256, embedding_type="fourier",
                  input_channels=4, spatial_channels=1, dropout=0.0, centered=False, discriminative=False, **kwargs):
         super().__init__()
+        # Accepted beyond the StoRM default set: fir=False (with progressive='none'), skip_rescale=False, progressive='none',
+        # progressive_input='none', progressive_combine='cat', centered=True, conditional / scale_by_sigma = False, any dropout (identity at
+        # inference: the reference runs eval()).  What stays refused, and why:
+        progressive, progressive_input = progressive.lower(), progressive_input.lower()
+        progressive_combine, resblock_type, embedding_type = progressive_combine.lower(), resblock_type.lower(), embedding_type.lower()
         unsupported = []
-        if nonlinearity != "swish": unsupported.append(f"nonlinearity={nonlinearity}")
-        if not fir or list(fir_kernel) != [1, 3, 3, 1]: unsupported.append("fir / fir_kernel")
-        if not skip_rescale: unsupported.append("skip_rescale=False")
-        if resblock_type.lower() != "biggan": unsupported.append(f"resblock_type={resblock_type}")
-        if progressive.lower() != "output_skip": unsupported.append(f"progressive={progressive}")
-        if progressive_input.lower() != "input_skip": unsupported.append(f"progressive_input={progressive_input}")
-        if progressive_combine.lower() != "sum": unsupported.append(f"progressive_combine={progressive_combine}")
-        if embedding_type.lower() != "fourier": unsupported.append(f"embedding_type={embedding_type}")
-        if spatial_channels != 1: unsupported.append(f"spatial_channels={spatial_channels}")
-        if dropout != 0.0: unsupported.append("dropout (inference engine)")
-        if centered: unsupported.append("centered=True")
-        if not discriminative and (not conditional or not scale_by_sigma):
-            unsupported.append("conditional / scale_by_sigma = False on a score network")
+        if nonlinearity != "swish":
+            unsupported.append(f"nonlinearity={nonlinearity} (SiLU is fused into the operand rewrite of the convolution kernels)")
+        if list(fir_kernel) != [1, 3, 3, 1]:
+            unsupported.append(f"fir_kernel={list(fir_kernel)} (the FIR kernels hold the taps [1, 3, 3, 1])")
+        if resblock_type != "biggan":
+            unsupported.append(f"resblock_type={resblock_type} (ddpm blocks resample with FIR fused into a strided / transposed 3x3 convolution: "
+                               "a kernel family this engine does not have)")
+        if progressive not in ("output_skip", "none"):
+            unsupported.append(f"progressive={progressive} ('residual' needs FIR fused into a transposed 3x3 convolution)")
+        if progressive_input not in ("input_skip", "none"):
+            unsupported.append(f"progressive_input={progressive_input} ('residual' needs FIR fused into a strided 3x3 convolution)")
+        if progressive_combine not in ("sum", "cat"):
+            unsupported.append(f"progressive_combine={progressive_combine} (the reference knows 'sum' and 'cat')")
+        if not fir and progressive == "output_skip":
+            unsupported.append("fir=False with progressive='output_skip' (the reference itself fails there: layerspp.py:117 passes 'nearest' "
+                               "as scale_factor - ValueError; use progressive='none')")
+        if embedding_type != "fourier":
+            unsupported.append(f"embedding_type={embedding_type} (the reference's own forward reads self.sigmas, which NCSNpp never defines: "
+                               "ncsnpp.py:304-308 - AttributeError)")
+        if spatial_channels != 1:
+            unsupported.append(f"spatial_channels={spatial_channels} (single-channel spectrograms only)")
         if unsupported:
-            raise NotImplementedError("storm_amd NCSNpp covers the StoRM hot-path configuration only; unsupported: "
-                                      + ", ".join(unsupported))
+            raise NotImplementedError("storm_amd NCSNpp: unsupported constructor options: " + "; ".join(unsupported))
         self.FORCE_STFT_OUT = False
         if discriminative:
             print("Running NCSN++ as discriminative backbone")
@@ -130,7 +142,10 @@ class NCSNpp(nn.Module):
         self.cfg = NCSNppConfig(nf=nf, ch_mult=tuple(ch_mult), num_res_blocks=num_res_blocks,
                                 attn_resolutions=tuple(attn_resolutions), image_size=image_size,
                                 input_channels=input_channels, discriminative=discriminative,
-                                fourier_scale=float(fourier_scale))
+                                fourier_scale=float(fourier_scale), fir=bool(fir), skip_rescale=bool(skip_rescale),
+                                progressive=progressive == "output_skip", progressive_input=progressive_input == "input_skip",
+                                combine_cat=progressive_combine == "cat", centered=bool(centered),
+                                time_conditional=bool(conditional), sigma_scaling=bool(scale_by_sigma))
         self.nf, self.discriminative, self.input_channels = nf, discriminative, input_channels
         self.spatial_channels = 1
         total = self.cfg.total_channels
@@ -213,9 +228,7 @@ class NCSNpp(nn.Module):
         except Exception:
             pass
 
-    def c_config(self):
-        """the storm_ncsnpp_config of this network (include/storm_hip.h)"""
-        c = L.NcsnppConfig()
+    def _fill_config(self, c):
         c.nf, c.n_levels, c.num_res_blocks = self.cfg.nf, len(self.cfg.ch_mult), self.cfg.num_res_blocks
         for i, v in enumerate(self.cfg.ch_mult):
             c.ch_mult[i] = v
@@ -223,6 +236,19 @@ class NCSNpp(nn.Module):
         for i, v in enumerate(self.cfg.attn_resolutions):
             c.attn_resolutions[i] = v
         c.image_size, c.input_channels, c.discriminative = self.cfg.image_size, self.cfg.input_channels, int(self.cfg.discriminative)
+        return c
+
+    def c_config(self):
+        """the storm_ncsnpp_config of this network (include/storm_hip.h): the shape fields alone - it describes this network only when the
+        options are the defaults (c_config_ex carries them)"""
+        return self._fill_config(L.NcsnppConfig())
+
+    def c_config_ex(self):
+        """the storm_ncsnpp_config_ex of this network (include/storm_hip.h): shape fields + the constructor's options"""
+        c = self._fill_config(L.NcsnppConfigEx())
+        c.struct_size = C.sizeof(L.NcsnppConfigEx)
+        c.fir, c.skip_rescale, c.progressive, c.progressive_input = int(self.cfg.fir), int(self.cfg.skip_rescale), int(self.cfg.progressive), int(self.cfg.progressive_input)
+        c.combine_cat, c.centered, c.conditional, c.scale_by_sigma = int(self.cfg.combine_cat), int(self.cfg.centered), int(self.cfg.time_conditional), int(self.cfg.sigma_scaling)
         return c
 
     def _get_handle(self, dtype_code, device):
@@ -234,16 +260,18 @@ class NCSNpp(nn.Module):
         if ent is not None:
             L.lib().storm_ncsnpp_destroy(ent[0])
             self._workspaces.clear()
-        cfg = self.c_config()
+        cfg = self.c_config_ex()
         lib = L.lib()
         sd = [v.detach().to(device=device, dtype=torch.float32).contiguous() for v in self.state_dict().values()]
-        n = lib.storm_ncsnpp_num_tensors(C.byref(cfg))
+        n = lib.storm_ncsnpp_num_tensors_ex(C.byref(cfg))
+        if n < 0:
+            raise L.StormError(f"storm_ncsnpp_num_tensors_ex: {lib.storm_last_error().decode()}")
         if n != len(sd):
             raise L.StormError(f"state_dict has {len(sd)} tensors, the engine's enumeration {n}")
         ptrs = (C.c_void_p * n)(*[L.ptr(t) for t in sd])
-        arena = torch.empty(lib.storm_ncsnpp_arena_bytes(C.byref(cfg), dtype_code), dtype=torch.uint8, device=device)
+        arena = torch.empty(lib.storm_ncsnpp_arena_bytes_ex(C.byref(cfg), dtype_code), dtype=torch.uint8, device=device)
         h = C.c_void_p()
-        L.check(lib.storm_ncsnpp_create(C.byref(cfg), ptrs, n, dtype_code, L.ptr(arena), L.stream(), C.byref(h)), "storm_ncsnpp_create")
+        L.check(lib.storm_ncsnpp_create_ex(C.byref(cfg), ptrs, n, dtype_code, L.ptr(arena), L.stream(), C.byref(h)), "storm_ncsnpp_create_ex")
         L.check(lib.storm_ncsnpp_set_fusion(h, int(os.environ.get("STORM_FUSE_GN_STATS", "1") != "0"),
                                             int(os.environ.get("STORM_FUSE_GN_APPLY", "1") != "0"),
                                             int(os.environ.get("STORM_FUSED_ATTENTION", "1") != "0")), "storm_ncsnpp_set_fusion")
@@ -323,7 +351,7 @@ class NCSNpp(nn.Module):
                 raise TypeError("inputs must be complex64 tensors of identical shape")
             parts[j] = L.ptr(torch.view_as_real(t_in))
         tc = None
-        if self.cfg.conditional:
+        if self.cfg.needs_t:
             if time_cond is None:
                 raise ValueError("time_cond is required for a score network")
             tc = time_cond.to(device=dev, dtype=torch.float32).contiguous()
@@ -358,7 +386,7 @@ class NCSNpp(nn.Module):
                 if t_in.dtype != torch.complex64 or t_in.shape != x0.shape or not t_in.is_contiguous():
                     raise TypeError("inputs must be contiguous complex64 tensors of identical shape per problem")
                 parts[p * n_parts + j] = L.ptr(torch.view_as_real(t_in))
-            if self.cfg.conditional:
+            if self.cfg.needs_t:
                 if time_conds is None or time_conds[p] is None:
                     raise ValueError("time_cond is required for a score network")
                 tc = time_conds[p].to(device=dev, dtype=torch.float32).contiguous()
@@ -381,7 +409,7 @@ class NCSNpp(nn.Module):
                 ws = torch.empty(n, dtype=torch.uint8, device=dev)
             self._workspaces[key] = ws
             # (launched under the lock: host threads that share this stream's scratch must not interleave the launches of two evaluations)
-            L.check(L.lib().storm_ncsnpp_forward_group(h, P, Bs, Ts, F, parts, n_parts, tptr if self.cfg.conditional else None, optr, L.ptr(ws), ws.numel(),
+            L.check(L.lib().storm_ncsnpp_forward_group(h, P, Bs, Ts, F, parts, n_parts, tptr if self.cfg.needs_t else None, optr, L.ptr(ws), ws.numel(),
                                                        int(self.negate_output), L.stream()), "storm_ncsnpp_forward_group")
         return outs
 

@@ -14,7 +14,7 @@ from .. import _lib as L
 
 # op codes (include/storm_hip.h)
 OP_MEMSET, OP_PACK_INPUT, OP_TEMB, OP_DENSE, OP_CONV, OP_GN_STATS, OP_GN_APPLY, OP_FIR_UP, OP_FIR_DOWN, \
-    OP_SOFTMAX, OP_OUTPUT_HEAD, OP_GN_FINALIZE, OP_ATTENTION, OP_INPUT_PYRAMID, OP_OUTPUT_PYRAMID = range(15)
+    OP_SOFTMAX, OP_OUTPUT_HEAD, OP_GN_FINALIZE, OP_ATTENTION, OP_INPUT_PYRAMID, OP_OUTPUT_PYRAMID, OP_COMBINE_CAT = range(16)
 
 # buffer slots of storm_program_run
 BUF_WS, BUF_PARAMS, BUF_IN0, BUF_IN1, BUF_IN2, BUF_T, BUF_OUT = range(7)
@@ -38,10 +38,27 @@ class NCSNppConfig:
     input_channels: int = 4
     discriminative: bool = False
     fourier_scale: float = 16.0
+    # the constructor's other graph-shaping options (storm_ncsnpp_config_ex, include/storm_hip.h); the defaults are the StoRM set
+    fir: bool = True                    # False: nearest x2 / 2x2 mean resampling (only with progressive=False: the reference's own limit)
+    skip_rescale: bool = True
+    progressive: bool = True            # 'output_skip' (True) / 'none' (False)
+    progressive_input: bool = True      # 'input_skip' (True) / 'none' (False)
+    combine_cat: bool = False           # progressive_combine: 'sum' (False) / 'cat' (True)
+    centered: bool = False
+    time_conditional: bool = True       # the constructor's `conditional`
+    sigma_scaling: bool = True          # the constructor's `scale_by_sigma`
 
     @property
     def conditional(self):
-        return not self.discriminative
+        return self.time_conditional and not self.discriminative
+
+    @property
+    def scale_by_sigma(self):
+        return self.sigma_scaling and not self.discriminative
+
+    @property
+    def needs_t(self):
+        return self.conditional or self.scale_by_sigma
 
     @property
     def total_channels(self):
@@ -68,7 +85,10 @@ def module_list(cfg: NCSNppConfig):
             hs_c.append(in_ch)
         if lvl != nres - 1:
             mods.append(("res", dict(i=in_ch, o=in_ch, resample=True)))
-            mods.append(("combine", dict(i=total, o=in_ch)))
+            if cfg.progressive_input:
+                mods.append(("combine", dict(i=total, o=in_ch)))
+                if cfg.combine_cat:
+                    in_ch *= 2
             hs_c.append(in_ch)
     in_ch = hs_c[-1]
     mods += [("res", dict(i=in_ch, o=in_ch, resample=False)), ("attn", dict(c=in_ch)),
@@ -80,11 +100,15 @@ def module_list(cfg: NCSNppConfig):
             in_ch = out_ch
         if all_res[lvl] in cfg.attn_resolutions:
             mods.append(("attn", dict(c=in_ch)))
-        mods.append(("gn", dict(c=in_ch)))
-        mods.append(("conv3", dict(i=in_ch, o=total)))
+        if cfg.progressive:
+            mods.append(("gn", dict(c=in_ch)))
+            mods.append(("conv3", dict(i=in_ch, o=total)))
         if lvl != 0:
             mods.append(("res", dict(i=in_ch, o=in_ch, resample=True)))
     assert not hs_c
+    if not cfg.progressive:             # the head of progressive='none' (ncsnpp.py:258-263)
+        mods.append(("gn", dict(c=in_ch)))
+        mods.append(("conv3", dict(i=in_ch, o=total)))
     return mods
 
 

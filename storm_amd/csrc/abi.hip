@@ -77,6 +77,7 @@ extern "C" long long storm_abi_struct_bytes(int which) {
         case 1: return (long long)sizeof(storm_op);
         case 2: return (long long)sizeof(storm_conv_seg);
         case 3: return (long long)sizeof(storm_ncsnpp_config);
+        case 4: return (long long)sizeof(storm_ncsnpp_config_ex);
         default: return -1;
     }
 }

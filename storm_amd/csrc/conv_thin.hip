@@ -274,6 +274,72 @@ int launch_conv_thin(const storm_conv_args& a, hipStream_t st) {
     return nine ? launch_thin<bf16_t, 9>(a, st) : launch_thin<bf16_t, 1>(a, st);
 }
 
+// ---- Combine(method='cat') (layerspp.py:44-59): out = cat([conv1x1(x) + bias, h], channel) ----------------------------------------
+// x is the 8-channel input-pyramid level, so the 1x1 is 8 multiply-adds per output and the op is bound by the 2 C channels it writes per
+// pixel: one pass writes the convolution into the channel slice [0, C) of the NHWC [npix][2 C] output and copies h into [C, 2 C) beside it
+// (nothing is written twice, torch.cat never materialises).  A thread owns one 16-byte channel slot of the output and walks CAT_PPT pixels:
+// a slot of the first half keeps its PER16 x 8 weights in registers (fp32 accumulation in input-channel order, one rounding), a slot of the
+// second half moves 16 bytes per pixel.  Consecutive lanes hold consecutive slots: whole lines per wave access.
+constexpr int CAT_PPT = 8;
+template <typename T>
+__global__ __launch_bounds__(256)
+void combine_cat_kernel(const T* __restrict__ x, const T* __restrict__ w, int CinP, const float* __restrict__ bias, const T* __restrict__ h,
+                        T* __restrict__ out, long long npix, int C) {
+    constexpr int PER16 = Elem<T>::PER16;
+    const int S = 2 * C / PER16;                                // slots of an output pixel
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int slot = (int)(g % S);
+    const long long p0 = g / S * CAT_PPT, p1 = p0 + CAT_PPT < npix ? p0 + CAT_PPT : npix;
+    if (p0 >= npix) return;
+    const int c = slot * PER16;
+    if (c >= C) {                                               // the copy of h
+        for (long long px = p0; px < p1; ++px)
+            *reinterpret_cast<uint4*>(out + px * 2 * C + c) = *reinterpret_cast<const uint4*>(h + px * C + (c - C));
+        return;
+    }
+    float wr[PER16][8], b[PER16];
+#pragma unroll
+    for (int e = 0; e < PER16; ++e) {
+        b[e] = bias ? bias[c + e] : 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) wr[e][k] = to_f32(w[(long long)(c + e) * CinP + k]);
+    }
+    for (long long px = p0; px < p1; ++px) {
+        float xv[8];
+        load8(x + px * 8, xv);
+        alignas(16) T ov[PER16];
+#pragma unroll
+        for (int e = 0; e < PER16; ++e) {
+            float acc = b[e];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc = fmaf(wr[e][k], xv[k], acc);
+            from_f32(ov[e], acc);
+        }
+        *reinterpret_cast<uint4*>(out + px * 2 * C + c) = *reinterpret_cast<const uint4*>(ov);
+    }
+}
+}  // namespace storm
+
+extern "C" int storm_combine_cat(const void* x, const void* w, int CinP, const float* bias, const void* h, void* out, long long npix, int C,
+                                 int dtype, storm_stream_t s) {
+    using namespace storm;
+    STORM_CHECK(x && w && h && out && npix > 0, "storm_combine_cat: null pointer");
+    STORM_CHECK(C > 0 && C % 8 == 0 && CinP >= 8, "storm_combine_cat: C=%d CinP=%d", C, CinP);
+    const int per16 = dtype == STORM_F32 ? 4 : 8;
+    const long long threads = (npix + CAT_PPT - 1) / CAT_PPT * (2 * C / per16), grid = (threads + 255) / 256;
+    STORM_CHECK(grid < (1LL << 31), "storm_combine_cat: grid %lld out of range", grid);
+    hipStream_t st = (hipStream_t)s;
+#define STORM_CAT(T_) hipLaunchKernelGGL((combine_cat_kernel<T_>), dim3((unsigned)grid), dim3(256), 0, st, (const T_*)x, (const T_*)w, CinP, bias, (const T_*)h, (T_*)out, npix, C)
+    if (dtype == STORM_BF16) STORM_CAT(bf16_t);
+    else if (dtype == STORM_F16) STORM_CAT(half_t);
+    else if (dtype == STORM_F32) STORM_CAT(float);
+    else STORM_CHECK(false, "storm_combine_cat: dtype %d", dtype);
+#undef STORM_CAT
+    STORM_LAUNCH_CHECK();
+    return STORM_OK;
+}
+
+namespace storm {
 const char* conv_thin_kernel_name(int dtype, int ntaps) {
     if (dtype == STORM_F16) return ntaps == 9 ? "storm::conv_thin_kernel<storm::half_t, 9>" : "storm::conv_thin_kernel<storm::half_t, 1>";
     return ntaps == 9 ? "storm::conv_thin_kernel<storm::bf16_t, 9>" : "storm::conv_thin_kernel<storm::bf16_t, 1>";

@@ -36,7 +36,12 @@ struct Module { Kind kind; int i = 0, o = 0, c = 0, n = 0; bool resample = false
 struct Cfg {
     int nf = 128; std::vector<int> ch_mult{1, 2, 2, 2}; int num_res_blocks = 1; std::vector<int> attn_res{0};
     int image_size = 256, input_channels = 4; bool discriminative = false;
-    bool conditional() const { return !discriminative; }
+    // the constructor's graph-shaping options beyond the StoRM default set (storm_ncsnpp_config_ex; ncsnpp.py:40-147)
+    bool fir = true, skip_rescale = true, progressive = true, progressive_input = true, combine_cat = false, centered = false;
+    bool time_conditional = true, sigma_scaling = true;
+    bool conditional() const { return time_conditional && !discriminative; }
+    bool scale_by_sigma() const { return sigma_scaling && !discriminative; }
+    float res_scale() const { return skip_rescale ? (float)(1.0 / std::sqrt(2.0)) : 1.0f; }
     int total() const { return discriminative ? 2 : input_channels; }
 };
 
@@ -64,7 +69,7 @@ static std::vector<Module> module_list(const Cfg& c) {
         }
         if (lvl != nres - 1) {
             add(RES, in_ch, in_ch, 0, 0, true);
-            add(COMBINE, total, in_ch, 0, 0, false);
+            if (c.progressive_input) { add(COMBINE, total, in_ch, 0, 0, false); if (c.combine_cat) in_ch *= 2; }
             hs_c.push_back(in_ch);
         }
     }
@@ -78,10 +83,10 @@ static std::vector<Module> module_list(const Cfg& c) {
             in_ch = out_ch;
         }
         if (in_list(c.attn_res, all_res[lvl])) add(ATTN, 0, 0, in_ch, 0, false);
-        add(GN, 0, 0, in_ch, 0, false);
-        add(CONV3, in_ch, total, 0, 0, false);
+        if (c.progressive) { add(GN, 0, 0, in_ch, 0, false); add(CONV3, in_ch, total, 0, 0, false); }
         if (lvl != 0) add(RES, in_ch, in_ch, 0, 0, true);
     }
+    if (!c.progressive) { add(GN, 0, 0, in_ch, 0, false); add(CONV3, in_ch, total, 0, 0, false); }    // the head of progressive='none' (ncsnpp.py:258-263)
     return m;
 }
 
@@ -262,7 +267,8 @@ struct Program {
             ws(o, 0, xa.off); if (xb) ws(o, 1, xb->off); ws(o, 2, st);
             o.i[0] = xa.C; o.i[1] = xb ? xb->C : 0; o.i[2] = B; o.i[3] = (long long)xa.H * xa.W; o.i[4] = G;
         }
-        const int OH = resample == 1 ? 2 * xa.H : (resample == 2 ? xa.H / 2 : xa.H), OW = resample == 1 ? 2 * xa.W : (resample == 2 ? xa.W / 2 : xa.W);
+        const bool r_up = resample == 1 || resample == 3, r_dn = resample == 2 || resample == 4;      // (3 / 4: the non-FIR members, fir=False)
+        const int OH = r_up ? 2 * xa.H : (r_dn ? xa.H / 2 : xa.H), OW = r_up ? 2 * xa.W : (r_dn ? xa.W / 2 : xa.W);
         Act out = new_act(OH, OW, Cc), raw;
         if (resample) raw = new_act(OH, OW, Cc);
         storm_op& o = op(STORM_OP_GN_APPLY);
@@ -345,7 +351,7 @@ struct Program {
     Act resblock(int idx, const Module& p, const Act& xa, const Act* xb, int resample) {
         const std::string k = "all_modules." + std::to_string(idx) + ".";
         const int o = p.o;
-        const float inv = (float)(1.0 / std::sqrt(2.0));
+        const float inv = cfg.res_scale();
         const bool fuse = fuse_apply && xa.part >= 0 && (!xb || xb->part >= 0);
         ConvOpt c0; c0.bias = k + "Conv_0.bias";
         if (cfg.conditional()) { c0.has_tb = true; c0.tb_off = dense_out + 4 * lay.dense_off.at(idx); c0.tb_stride = (int)lay.dense_rows; }
@@ -421,11 +427,28 @@ struct Program {
             free_act(P); free_act(vT);
         }
         Act xl = x; xl.H = 1; xl.W = Lp; xl.part = -1;
-        ConvOpt c3; c3.bias = k + "NIN_3.b"; c3.skip = &xl; c3.scale = (float)(1.0 / std::sqrt(2.0)); c3.want_part = fuse_stats;
+        ConvOpt c3; c3.bias = k + "NIN_3.b"; c3.skip = &xl; c3.scale = cfg.res_scale(); c3.want_part = fuse_stats;
         Act out = conv({wseg(o, k + "NIN_3.W", 1)}, Cc, 1, Lp, c3);
         free_act(o);
         out.H = x.H; out.W = x.W;
         return out;
+    }
+
+    // GroupNorm, act, conv3x3(C -> total_channels) of the output pyramid's levels / of the progressive='none' head (modules midx, midx + 1)
+    Act narrow_head(int midx, const Act& h) {
+        const std::string kg = "all_modules." + std::to_string(midx) + ".", kc = "all_modules." + std::to_string(midx + 1) + ".";
+        Act ph;
+        ConvOpt c; c.outC = 8; c.bias = kc + "bias";
+        if (fuse_apply && h.part >= 0) {
+            const long long ssp = gn_affine(h, nullptr, kg + "weight", kg + "bias");
+            ph = conv({wseg(h, kc + "weight", 9, nullptr, ssp)}, cfg.total(), h.H, h.W, c);
+            arena.release(ssp);
+        } else {
+            auto pr = gn(h, nullptr, kg + "weight", kg + "bias", true, 0);
+            ph = conv({wseg(pr.first, kc + "weight", 9)}, cfg.total(), h.H, h.W, c);
+            free_act(pr.first);
+        }
+        return ph;
     }
 
     int build() {
@@ -440,14 +463,16 @@ struct Program {
         const int n_in = total / 2;
         // the input pyramid (input_skip): a function of the network input alone, so every level is built here, ahead of the U-Net - the packing and
         // up to three FIR x2 down steps per launch (csrc/pyramid.hip; `ncsnpp`: one launch, `ncsnpplarge` with its six steps: two)
+        // (progressive_input='none': level 0 - the packing - alone; fir=False: the 2 x 2 mean chain; centered: no 2x - 1)
         std::vector<Act> ips;
-        for (int lvl = 0; lvl < nres; ++lvl) ips.push_back(new_act(F >> lvl, T >> lvl, 8));
-        for (int l0 = 0; l0 == 0 || l0 < nres - 1; l0 += 3) {
-            const int nl = std::min(4, nres - l0);
+        const int nlev = cfg.progressive_input ? nres : 1;
+        for (int lvl = 0; lvl < nlev; ++lvl) ips.push_back(new_act(F >> lvl, T >> lvl, 8));
+        for (int l0 = 0; l0 == 0 || l0 < nlev - 1; l0 += 3) {
+            const int nl = std::min(4, nlev - l0);
             storm_op& o = op(STORM_OP_INPUT_PYRAMID);
             if (l0 == 0) for (int j = 0; j < n_in; ++j) ref(o, j, BUF_IN0 + j, 0);
             for (int k = 0; k < nl; ++k) ws(o, 3 + k, ips[(size_t)(l0 + k)].off);
-            o.i[0] = l0 == 0 ? n_in : 0; o.i[1] = B; o.i[2] = F >> l0; o.i[3] = T >> l0; o.i[4] = nl;
+            o.i[0] = l0 == 0 ? n_in : 0; o.i[1] = B; o.i[2] = F >> l0; o.i[3] = T >> l0; o.i[4] = nl; o.i[5] = cfg.fir ? 0 : 1; o.i[6] = cfg.centered ? 1 : 0;
         }
         Act x0 = ips[0];
         int midx = 1;
@@ -472,11 +497,23 @@ struct Program {
                 hs.push_back(h);
             }
             if (lvl != nres - 1) {
-                Act h = resblock(midx, mods[midx], hs.back(), nullptr, 2); ++midx;
+                Act h = resblock(midx, mods[midx], hs.back(), nullptr, cfg.fir ? 2 : 4); ++midx;
+                if (!cfg.progressive_input) { hs.push_back(h); continue; }
                 free_act(ip); ip = ips[(size_t)lvl + 1];
                 const std::string kk = "all_modules." + std::to_string(midx) + ".";
-                ConvOpt c; c.bias = kk + "Conv_0.bias"; c.skip = &h; c.want_part = fuse_stats;
-                Act hc = conv({wseg(ip, kk + "Conv_0.weight", 1)}, h.C, h.H, h.W, c); ++midx;
+                Act hc;
+                if (cfg.combine_cat) {                           // Combine 'cat': cat([conv1x1(input pyramid), h]) in one pass (storm_combine_cat)
+                    const Entry& e = lay.at(kk + "Conv_0.weight");
+                    hc = new_act(h.H, h.W, 2 * h.C);
+                    storm_op& o = op(STORM_OP_COMBINE_CAT);
+                    ws(o, 0, ip.off); par(o, 1, kk + "Conv_0.weight"); par(o, 2, kk + "Conv_0.bias"); ws(o, 3, h.off); ws(o, 4, hc.off);
+                    o.i[0] = (long long)B * h.H * h.W; o.i[1] = h.C; o.i[2] = e.shape[2];
+                    flops += 2LL * B * h.H * h.W * h.C * total;
+                } else {
+                    ConvOpt c; c.bias = kk + "Conv_0.bias"; c.skip = &h; c.want_part = fuse_stats;
+                    hc = conv({wseg(ip, kk + "Conv_0.weight", 1)}, h.C, h.H, h.W, c);
+                }
+                ++midx;
                 free_act(h);
                 hs.push_back(hc);
             }
@@ -497,30 +534,20 @@ struct Program {
                 h = hn;
             }
             if (in_list(cfg.attn_res, h.H)) { Act hn = attnblock(midx, mods[midx], h); ++midx; free_act(h); h = hn; }
-            const std::string kg = "all_modules." + std::to_string(midx) + ".", kc = "all_modules." + std::to_string(midx + 1) + ".";
-            Act ph;
-            ConvOpt c; c.outC = 8; c.bias = kc + "bias";
-            if (fuse_apply && h.part >= 0) {
-                const long long ssp = gn_affine(h, nullptr, kg + "weight", kg + "bias");
-                ph = conv({wseg(h, kc + "weight", 9, nullptr, ssp)}, total, h.H, h.W, c);
-                arena.release(ssp);
-            } else {
-                auto pr = gn(h, nullptr, kg + "weight", kg + "bias", true, 0);
-                ph = conv({wseg(pr.first, kc + "weight", 9)}, total, h.H, h.W, c);
-                free_act(pr.first);
-            }
-            midx += 2;
-            phs.push_back(ph);                                   // (coarsest first; the up chain and the head run in ONE launch at the end)
-            if (lvl != 0) { Act hn = resblock(midx, mods[midx], h, nullptr, 1); ++midx; free_act(h); h = hn; }
+            if (cfg.progressive) { phs.push_back(narrow_head(midx, h)); midx += 2; }    // (coarsest first; the up chain and the head run in ONE launch at the end)
+            if (lvl != 0) { Act hn = resblock(midx, mods[midx], h, nullptr, cfg.fir ? 1 : 3); ++midx; free_act(h); h = hn; }
         }
+        if (!cfg.progressive) { phs.push_back(narrow_head(midx, h)); midx += 2; }       // progressive='none': GroupNorm, act, conv3x3 on the last h (ncsnpp.py:430-436)
         if (!hs.empty() || midx != (int)mods.size()) { set_error("storm_ncsnpp: planner walked %d of %zu modules", midx, mods.size()); return STORM_ERR_INVALID; }
         free_act(h);
-        // output pyramid (output_skip) + head: p = ph_0 + up(ph_1 + up(ph_2 + ...)), then output_layer / t - one launch (csrc/pyramid.hip)
+        // output pyramid (output_skip) + head: p = ph_0 + up(ph_1 + up(ph_2 + ...)), then output_layer / t - one launch (csrc/pyramid.hip);
+        // progressive='none': the same launch over the one level there is
+        const int npl = (int)phs.size();
         storm_op& o = op(STORM_OP_OUTPUT_PYRAMID);
-        for (int k = 0; k < nres; ++k) ws(o, k, phs[(size_t)(nres - 1 - k)].off);
-        if (cfg.conditional()) ref(o, 8, BUF_T, 0);
+        for (int k = 0; k < npl; ++k) ws(o, k, phs[(size_t)(npl - 1 - k)].off);
+        if (cfg.scale_by_sigma()) ref(o, 8, BUF_T, 0);
         par(o, 9, "output_layer.weight"); par(o, 10, "output_layer.bias"); ref(o, 11, BUF_OUT, 0);
-        o.i[0] = total; o.i[1] = B; o.i[2] = F; o.i[3] = T; o.i[4] = 0; o.i[5] = nres;
+        o.i[0] = total; o.i[1] = B; o.i[2] = F; o.i[3] = T; o.i[4] = 0; o.i[5] = npl;
         for (const Act& a : phs) free_act(a);
         ws_bytes = arena.top;
         return STORM_OK;
@@ -589,13 +616,47 @@ static int to_cfg(const storm_ncsnpp_config* c, Cfg& out) {
     return STORM_OK;
 }
 
-extern "C" int storm_ncsnpp_num_tensors(const storm_ncsnpp_config* c) {
-    Cfg cfg; if (to_cfg(c, cfg) != STORM_OK) return -1;
+// the extended description: the size the caller compiled is checked before anything else is read
+static int to_cfg_ex(const storm_ncsnpp_config_ex* c, Cfg& out) {
+    STORM_CHECK(c != nullptr, "storm_ncsnpp: null config");
+    STORM_CHECK(c->struct_size == (int)sizeof(storm_ncsnpp_config_ex), "storm_ncsnpp: storm_ncsnpp_config_ex.struct_size = %d, this library's is %d",
+                c->struct_size, (int)sizeof(storm_ncsnpp_config_ex));
+    storm_ncsnpp_config b;
+    b.nf = c->nf; b.n_levels = c->n_levels; memcpy(b.ch_mult, c->ch_mult, sizeof(b.ch_mult)); b.num_res_blocks = c->num_res_blocks; b.n_attn = c->n_attn;
+    memcpy(b.attn_resolutions, c->attn_resolutions, sizeof(b.attn_resolutions)); b.image_size = c->image_size; b.input_channels = c->input_channels;
+    b.discriminative = c->discriminative;
+    if (int rc = to_cfg(&b, out)) return rc;
+    STORM_CHECK(c->fir != 0 || c->progressive == 0, "storm_ncsnpp: fir=False with progressive='output_skip' is refused - the reference itself fails there "
+                "(layerspp.py:117 passes 'nearest' as scale_factor); use progressive='none'");
+    out.fir = c->fir != 0; out.skip_rescale = c->skip_rescale != 0; out.progressive = c->progressive != 0; out.progressive_input = c->progressive_input != 0;
+    out.combine_cat = c->combine_cat != 0; out.centered = c->centered != 0; out.time_conditional = c->conditional != 0; out.sigma_scaling = c->scale_by_sigma != 0;
+    return STORM_OK;
+}
+static void to_ex(const storm_ncsnpp_config* c, storm_ncsnpp_config_ex& e) {      // the plain description = the extended one with the default options
+    memset(&e, 0, sizeof(e));
+    STORM_NCSNPP_CONFIG_EX_DEFAULTS(&e);
+    e.nf = c->nf; e.n_levels = c->n_levels; memcpy(e.ch_mult, c->ch_mult, sizeof(e.ch_mult)); e.num_res_blocks = c->num_res_blocks; e.n_attn = c->n_attn;
+    memcpy(e.attn_resolutions, c->attn_resolutions, sizeof(e.attn_resolutions)); e.image_size = c->image_size; e.input_channels = c->input_channels;
+    e.discriminative = c->discriminative;
+}
+
+extern "C" int storm_ncsnpp_num_tensors_ex(const storm_ncsnpp_config_ex* c) {
+    Cfg cfg; if (to_cfg_ex(c, cfg) != STORM_OK) return -1;
     return (int)state_dict(cfg).size();
+}
+extern "C" int storm_ncsnpp_num_tensors(const storm_ncsnpp_config* c) {
+    if (c == nullptr) { set_error("storm_ncsnpp: null config"); return -1; }
+    storm_ncsnpp_config_ex e; to_ex(c, e);
+    return storm_ncsnpp_num_tensors_ex(&e);
 }
 
 extern "C" int storm_ncsnpp_tensor_info(const storm_ncsnpp_config* c, int i, char* name, int name_len, int* ndim, long long* shape4) {
-    Cfg cfg; if (int rc = to_cfg(c, cfg)) return rc;
+    STORM_CHECK(c != nullptr, "storm_ncsnpp: null config");
+    storm_ncsnpp_config_ex e; to_ex(c, e);
+    return storm_ncsnpp_tensor_info_ex(&e, i, name, name_len, ndim, shape4);
+}
+extern "C" int storm_ncsnpp_tensor_info_ex(const storm_ncsnpp_config_ex* c, int i, char* name, int name_len, int* ndim, long long* shape4) {
+    Cfg cfg; if (int rc = to_cfg_ex(c, cfg)) return rc;
     const auto sd = state_dict(cfg);
     STORM_CHECK(i >= 0 && i < (int)sd.size() && name && name_len > 0 && ndim && shape4, "storm_ncsnpp_tensor_info: bad arguments");
     snprintf(name, (size_t)name_len, "%s", sd[i].name.c_str());
@@ -604,18 +665,29 @@ extern "C" int storm_ncsnpp_tensor_info(const storm_ncsnpp_config* c, int i, cha
     return STORM_OK;
 }
 
-extern "C" long long storm_ncsnpp_arena_bytes(const storm_ncsnpp_config* c, int dtype) {
-    Cfg cfg; if (to_cfg(c, cfg) != STORM_OK) return -1;
+extern "C" long long storm_ncsnpp_arena_bytes_ex(const storm_ncsnpp_config_ex* c, int dtype) {
+    Cfg cfg; if (to_cfg_ex(c, cfg) != STORM_OK) return -1;
     return make_layout(cfg, dtype).size;
+}
+extern "C" long long storm_ncsnpp_arena_bytes(const storm_ncsnpp_config* c, int dtype) {
+    if (c == nullptr) { set_error("storm_ncsnpp: null config"); return -1; }
+    storm_ncsnpp_config_ex e; to_ex(c, e);
+    return storm_ncsnpp_arena_bytes_ex(&e, dtype);
 }
 
 // weights: device fp32 tensors of the reference state_dict, in ITS order (storm_ncsnpp_tensor_info); arena: device buffer of
 // storm_ncsnpp_arena_bytes() bytes owned by the caller, or NULL (the handle allocates and owns one).
 extern "C" int storm_ncsnpp_create(const storm_ncsnpp_config* c, const void* const* weights, int n_weights, int dtype, void* arena,
                                    storm_stream_t s, storm_ncsnpp** out) {
+    STORM_CHECK(c != nullptr, "storm_ncsnpp: null config");
+    storm_ncsnpp_config_ex e; to_ex(c, e);
+    return storm_ncsnpp_create_ex(&e, weights, n_weights, dtype, arena, s, out);
+}
+extern "C" int storm_ncsnpp_create_ex(const storm_ncsnpp_config_ex* c, const void* const* weights, int n_weights, int dtype, void* arena,
+                                      storm_stream_t s, storm_ncsnpp** out) {
     STORM_CHECK(out != nullptr && weights != nullptr, "storm_ncsnpp_create: null argument");
     STORM_CHECK(dtype == STORM_F32 || dtype == STORM_BF16 || dtype == STORM_F16, "storm_ncsnpp_create: dtype %d", dtype);
-    Cfg cfg; if (int rc = to_cfg(c, cfg)) return rc;
+    Cfg cfg; if (int rc = to_cfg_ex(c, cfg)) return rc;
     const auto sd = state_dict(cfg);
     STORM_CHECK(n_weights == (int)sd.size(), "storm_ncsnpp_create: %d weight tensors given, the configuration has %zu", n_weights, sd.size());
     std::map<std::string, int> by_name;
@@ -851,7 +923,7 @@ extern "C" int storm_ncsnpp_forward(storm_ncsnpp* h, const void* const* parts, i
     STORM_CHECK(parts && out && ws, "storm_ncsnpp_forward: null pointer");
     STORM_CHECK(n_parts == h->cfg.total() / 2, "storm_ncsnpp_forward: %d complex input channels given, the network takes %d", n_parts, h->cfg.total() / 2);
     STORM_CHECK(ws_bytes >= p->ws_bytes, "storm_ncsnpp_forward: workspace %lld < %lld bytes", ws_bytes, p->ws_bytes);
-    STORM_CHECK(!h->cfg.conditional() || t != nullptr, "storm_ncsnpp_forward: a score network needs t");
+    STORM_CHECK(!(h->cfg.conditional() || h->cfg.scale_by_sigma()) || t != nullptr, "storm_ncsnpp_forward: a score network needs t");
     void* bufs[N_BUFS] = {nullptr};
     bufs[BUF_WS] = ws; bufs[BUF_PARAMS] = h->arena;
     for (int j = 0; j < n_parts; ++j) { STORM_CHECK(parts[j] != nullptr, "storm_ncsnpp_forward: input %d is NULL", j); bufs[BUF_IN0 + j] = const_cast<void*>(parts[j]); }
@@ -920,7 +992,7 @@ extern "C" int storm_ncsnpp_forward_group(storm_ncsnpp* h, int P, const int* B, 
     STORM_CHECK(parts && out && ws, "storm_ncsnpp_forward_group: null pointer");
     STORM_CHECK(n_parts == h->cfg.total() / 2, "storm_ncsnpp_forward_group: %d complex input channels given, the network takes %d", n_parts, h->cfg.total() / 2);
     STORM_CHECK(ws_bytes >= gp->ws_bytes, "storm_ncsnpp_forward_group: workspace %lld < %lld bytes", ws_bytes, gp->ws_bytes);
-    STORM_CHECK(!h->cfg.conditional() || t != nullptr, "storm_ncsnpp_forward_group: a score network needs t");
+    STORM_CHECK(!(h->cfg.conditional() || h->cfg.scale_by_sigma()) || t != nullptr, "storm_ncsnpp_forward_group: a score network needs t");
     std::vector<void*> bufs((size_t)P * N_BUFS, nullptr);
     std::vector<void* const*> bufp((size_t)P);
     std::vector<const storm_op*> ops((size_t)P);

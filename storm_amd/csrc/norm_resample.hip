@@ -804,6 +804,113 @@ void gn_apply_up_group_kernel(const GnApplyProblem* __restrict__ tab, const GnFi
                       static_cast<T*>(q.out_act), static_cast<T*>(q.out_raw), q.ncg, q.nstrips, nt_stores, it.b, blockIdx.x);
 }
 
+// ---- the non-FIR members (fir=False) -----------------------------------------------------------------------------------------------
+// BigGAN up / down blocks of a network built with fir=False resample h = SiLU(GN(x)) AND the raw x with naive_upsample_2d (nearest x2) /
+// naive_downsample_2d (2 x 2 mean) (layerspp.py:246-258, up_or_down_sampling.py:164-178).  Same arguments, outputs and launch geometry as the
+// FIR kernels above: a thread owns one 16-byte channel slot of one column and walks down a strip of rows.
+//   MODE 3, nearest x2 up: column = INPUT column; per input row one load, normalised + activated once, eight 16-byte stores (the 2 x 2
+//           block of both tensors).  The raw tensor is a copy of the loaded bits; the activated one is rounded once.
+//   MODE 4, 2 x 2 mean down: column = OUTPUT column; per output row four loads; the mean of the four (activated) values is taken in fp32,
+//           ((x00 + x01) + (x10 + x11)) / 4, and rounded once; two stores.
+// No value is shared between rows, so there is no carry and no LDS beyond the per-channel (scale, shift) table.
+constexpr int NV_ROWS = 16;                         // rows per strip (input rows up, output rows down)
+template <typename T, bool SILU, int NS, int MODE>
+__global__ __launch_bounds__(256)
+void gn_apply_naive_kernel(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb, int H, int W, int G, const double* __restrict__ stats,
+          const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* __restrict__ out_act, T* __restrict__ out_raw,
+          int ncg, int nstrips, int nt_stores) {
+    constexpr int PER16 = Elem<T>::PER16;
+    constexpr int CG = NS * PER16;
+    constexpr int COLS = 256 / NS;                  // columns per workgroup
+    __shared__ float gtab[2 * CG];
+    const int C = Ca + Cb, tid = threadIdx.x;
+    const int slot = tid % NS, col = tid / NS;
+    int t = blockIdx.y;                             // (channel group, strip, batch item)
+    const int cg = t % ncg; t /= ncg;
+    const int strip = t % nstrips, b = t / nstrips;
+    const int gs = C / G;
+    if (tid < CG) {                                 // (scale, shift) of this workgroup's channels: y = x * sc + sh
+        const int cc = cg * CG + tid;
+        float sc = 0.f, sh = 0.f;
+        if (cc < C) {
+            const double n = (double)gs * H * W;
+            const int g = cc / gs;
+            const double m = stats[((long long)b * G + g) * 2] / n;
+            double var = stats[((long long)b * G + g) * 2 + 1] / n - m * m;
+            if (var < 0.0) var = 0.0;
+            const float pm = (float)m;
+            sc = (float)(1.0 / sqrt(var + (double)eps)) * gamma[cc];
+            sh = beta[cc] - pm * sc;
+        }
+        gtab[2 * tid] = sc; gtab[2 * tid + 1] = sh;
+    }
+    __syncthreads();
+    const int LH = MODE == 3 ? H : H / 2, LW = MODE == 3 ? W : W / 2;     // the image the threads walk
+    const int OH = MODE == 3 ? 2 * H : H / 2, OW = MODE == 3 ? 2 * W : W / 2;
+    const int c = cg * CG + slot * PER16;
+    const int lx = blockIdx.x * COLS + col;
+    if (c >= C || lx >= LW) return;
+    float pa[PER16], pb[PER16];
+#pragma unroll
+    for (int e = 0; e < PER16; ++e) { pa[e] = gtab[2 * (slot * PER16 + e)]; pb[e] = gtab[2 * (slot * PER16 + e) + 1]; }
+    const T* const src = (c < Ca) ? xa + c : xb + (c - Ca);
+    const int cs = (c < Ca) ? Ca : Cb;
+    const long long ibase = (long long)b * H * W;
+    const long long obase = (long long)b * OH * OW;
+    auto decode = [&](const uint4& q, float (&r)[PER16], float (&y)[PER16]) {      // the raw values and SiLU(GN(.)) of one slot, fp32
+        alignas(16) T raw[PER16];
+        *reinterpret_cast<uint4*>(raw) = q;
+#pragma unroll
+        for (int e = 0; e < PER16; ++e) {
+            r[e] = to_f32(raw[e]);
+            y[e] = fmaf(r[e], pa[e], pb[e]);
+            if (SILU) y[e] = silu_f(y[e]);
+        }
+    };
+    auto encode = [&](const float (&v)[PER16]) -> uint4 {
+        alignas(16) T ov[PER16];
+#pragma unroll
+        for (int e = 0; e < PER16; ++e) from_f32(ov[e], v[e]);
+        return *reinterpret_cast<const uint4*>(ov);
+    };
+    auto put = [&](T* dst, const uint4& q) {
+        if (nt_stores) store16_nt(dst, q);
+        else *reinterpret_cast<uint4*>(dst) = q;
+    };
+    const int rows = (LH + nstrips - 1) / nstrips;
+    const int y0 = strip * rows, y1 = min(LH, y0 + rows);
+    if (MODE == 3) {
+#pragma unroll 2
+        for (int iy = y0; iy < y1; ++iy) {
+            const uint4 q = *reinterpret_cast<const uint4*>(src + (ibase + (long long)iy * W + lx) * cs);
+            float r[PER16], y[PER16];
+            decode(q, r, y);
+            const uint4 qa = encode(y);
+            const long long o0 = (obase + (long long)(2 * iy) * OW + 2 * lx) * C + c, o1 = o0 + (long long)OW * C;
+            put(out_act + o0, qa); put(out_act + o0 + C, qa); put(out_act + o1, qa); put(out_act + o1 + C, qa);
+            if (out_raw != nullptr) { put(out_raw + o0, q); put(out_raw + o0 + C, q); put(out_raw + o1, q); put(out_raw + o1 + C, q); }
+        }
+    } else {
+#pragma unroll 2
+        for (int oy = y0; oy < y1; ++oy) {
+            const T* const row0 = src + (ibase + (long long)(2 * oy) * W + 2 * lx) * cs;
+            const T* const row1 = row0 + (long long)W * cs;
+            const uint4 q00 = *reinterpret_cast<const uint4*>(row0), q01 = *reinterpret_cast<const uint4*>(row0 + cs);
+            const uint4 q10 = *reinterpret_cast<const uint4*>(row1), q11 = *reinterpret_cast<const uint4*>(row1 + cs);
+            float r0[PER16], a0[PER16], r1[PER16], a1[PER16], r2[PER16], a2[PER16], r3[PER16], a3[PER16], va[PER16], vr[PER16];
+            decode(q00, r0, a0); decode(q01, r1, a1); decode(q10, r2, a2); decode(q11, r3, a3);
+#pragma unroll
+            for (int e = 0; e < PER16; ++e) {
+                va[e] = ((a0[e] + a1[e]) + (a2[e] + a3[e])) * 0.25f;
+                vr[e] = ((r0[e] + r1[e]) + (r2[e] + r3[e])) * 0.25f;
+            }
+            const long long o = (obase + (long long)oy * OW + lx) * C + c;
+            put(out_act + o, encode(va));
+            if (out_raw != nullptr) put(out_raw + o, encode(vr));
+        }
+    }
+}
+
 template <typename T, int RESAMPLE>
 __device__ __forceinline__ void fir_body(const T* __restrict__ x, const T* __restrict__ add, T* __restrict__ out,
                                          int H, int W, int C, int ppb, int C8, int PL, const int b) {
@@ -917,6 +1024,22 @@ static int gn_apply_t(const void* xa, int Ca, const void* xb, int Cb, int B, int
         if (silu) { if (NSr == 32) STORM_GN_UP(true, 32); else if (NSr == 16) STORM_GN_UP(true, 16); else STORM_GN_UP(true, 8); }
         else { if (NSr == 32) STORM_GN_UP(false, 32); else if (NSr == 16) STORM_GN_UP(false, 16); else STORM_GN_UP(false, 8); }
 #undef STORM_GN_UP
+        STORM_LAUNCH_CHECK();
+        return STORM_OK;
+    }
+    if (R == 3 || R == 4) {                              // the non-FIR members: nearest x2 up / 2 x 2 mean down (gn_apply_naive_kernel)
+        const int LH = R == 3 ? H : H / 2, LW = R == 3 ? W : W / 2;
+        STORM_CHECK(LH > 0 && LW > 0, "storm_gn_apply: empty image");
+        const int ncg = cdiv(Ca + Cb, NSr * Elem<T>::PER16), nstrips = cdiv(LH, strip_rows(LH, (long long)cdiv(LW, 256 / NSr) * ncg * B, NV_ROWS));
+        const long long gy = (long long)ncg * nstrips * B;
+        STORM_CHECK(gy < 65536, "storm_gn_apply: resampling grid %lld out of range", gy);
+        constexpr int M = R == 3 ? 3 : 4;
+        const int nt = R == 3 ? (switches().gn_nt & 1) : ((switches().gn_nt >> 1) & 1);
+#define STORM_GN_NV(SILU_, NS_) hipLaunchKernelGGL((gn_apply_naive_kernel<T, SILU_, NS_, M>), dim3(cdiv(LW, 256 / NS_), (unsigned)gy), dim3(256), 0, st, \
+                           (const T*)xa, Ca, (const T*)xb, Cb, H, W, G, stats, gamma, beta, eps, (T*)out_act, (T*)out_raw, ncg, nstrips, nt)
+        if (silu) { if (NSr == 32) STORM_GN_NV(true, 32); else if (NSr == 16) STORM_GN_NV(true, 16); else STORM_GN_NV(true, 8); }
+        else { if (NSr == 32) STORM_GN_NV(false, 32); else if (NSr == 16) STORM_GN_NV(false, 16); else STORM_GN_NV(false, 8); }
+#undef STORM_GN_NV
         STORM_LAUNCH_CHECK();
         return STORM_OK;
     }
@@ -1116,14 +1239,16 @@ extern "C" int storm_gn_apply(const void* xa, int Ca, const void* xb, int Cb, in
     if (int e = check_c("storm_gn_apply", Ca, Cb, groups)) return e;
     STORM_CHECK(xa && stats && gamma && beta && out_act, "storm_gn_apply: null pointer");
     STORM_CHECK((Cb == 0) == (xb == nullptr), "storm_gn_apply: xb / Cb mismatch");
-    STORM_CHECK(resample >= 0 && resample <= 2, "storm_gn_apply: resample=%d", resample);
-    STORM_CHECK(resample != 2 || (H % 2 == 0 && W % 2 == 0), "storm_gn_apply: FIR down needs even H, W");
+    STORM_CHECK(resample >= 0 && resample <= 4, "storm_gn_apply: resample=%d", resample);
+    STORM_CHECK((resample != 2 && resample != 4) || (H % 2 == 0 && W % 2 == 0), "storm_gn_apply: x2 down needs even H, W");
     hipStream_t st = (hipStream_t)s;
 #define STORM_GN_DISPATCH(T)                                                                                   \
     switch (resample) {                                                                                        \
         case 0: return gn_apply_t<T, 0>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, out_act, out_raw, st); \
         case 1: return gn_apply_t<T, 1>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, out_act, out_raw, st); \
-        default: return gn_apply_t<T, 2>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, out_act, out_raw, st); \
+        case 2: return gn_apply_t<T, 2>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, out_act, out_raw, st); \
+        case 3: return gn_apply_t<T, 3>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, out_act, out_raw, st); \
+        default: return gn_apply_t<T, 4>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, out_act, out_raw, st); \
     }
     if (dtype == STORM_BF16) { STORM_GN_DISPATCH(bf16_t) }
     if (dtype == STORM_F16) { STORM_GN_DISPATCH(half_t) }
@@ -1140,6 +1265,7 @@ extern "C" const char* storm_gn_apply_kernel_name(int C, int B, int H, int W, in
     if (resample == 0) { snprintf(name, sizeof(name), "storm::gn_apply_kernel<%s, 0>", tn); return name; }
     const int slots = C / per16;
     const int NSr = switches().gn_wide == 0 ? 8 : (slots % 32 == 0 ? 32 : slots % 16 == 0 ? 16 : 8);
+    if (resample >= 3) { snprintf(name, sizeof(name), "storm::gn_apply_naive_kernel<%s, %s, %d, %d>", tn, silu ? "true" : "false", NSr, resample); return name; }
     const bool share = resample == 2 && down_plan(C, B, H, W, per16, NSr).share;
     snprintf(name, sizeof(name), "storm::gn_apply_%s_kernel<%s, %s, %d>", resample == 1 ? "up" : share ? "down_share" : "down", tn, silu ? "true" : "false", NSr);
     return name;

@@ -117,12 +117,15 @@ static int run_ops(const storm_op* ops, int n_ops, void* const* bufs, int n_bufs
                 break;
             case STORM_OP_INPUT_PYRAMID: {
                 const float* in[3] = {(const float*)p[0], (const float*)p[1], (const float*)p[2]};
-                rc = storm_input_pyramid(i[0] > 0 ? in : nullptr, (int)i[0], p + 3, (int)i[4], (int)i[1], (int)i[2], (int)i[3], dtype, s);
+                rc = storm_input_pyramid_ex(i[0] > 0 ? in : nullptr, (int)i[0], p + 3, (int)i[4], (int)i[1], (int)i[2], (int)i[3], (int)i[5], (int)i[6], dtype, s);
                 break;
             }
             case STORM_OP_OUTPUT_PYRAMID:
                 rc = storm_output_pyramid(p, (int)i[5], (const float*)p[8], (const float*)p[9], (const float*)p[10], (int)i[0],
                                           (float*)p[11], (int)i[1], (int)i[2], (int)i[3], (int)i[4], dtype, s);
+                break;
+            case STORM_OP_COMBINE_CAT:
+                rc = storm_combine_cat(p[0], p[1], (int)i[2], (const float*)p[2], p[3], p[4], (long long)i[0], (int)i[1], dtype, s);
                 break;
             default:
                 STORM_CHECK(false, "storm_program_run: op %d has unknown code %d", k, op.code);

@@ -30,6 +30,7 @@ struct InParams {
     void* lvl[MAXD + 1];                     // level 0 .. nd: [B][H >> k][W >> k][8]
     int nd, B, H, W;                         // FIR steps of this launch; the level-0 image
     int th, tw, tiles_y, tiles_x;            // tile of the coarsest level per workgroup
+    int centered;                            // PACK: the data is already centred (centered=True, ncsnpp.py:325-327): no 2x - 1
 };
 struct OutParams {
     const void* ph[MAXL]; int nl;            // ph[k]: [B][H >> k][W >> k][8], finest first
@@ -39,13 +40,13 @@ struct OutParams {
 }  // namespace pyr
 
 // the network input of one pixel: x -> 2x - 1 on (re, im) of every complex input, zero padded to 8 channels (ncsnpp.py:289-296, 321-323)
-__device__ __forceinline__ void pack_pixel(const float* const (&in)[3], int n_in, long long i, float (&v)[8]) {
+__device__ __forceinline__ void pack_pixel(const float* const (&in)[3], int n_in, long long i, float (&v)[8], int centered = 0) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         if (k < n_in) {
             const float2 z = reinterpret_cast<const float2*>(in[k])[i];
-            v[2 * k] = 2.0f * z.x - 1.0f;
-            v[2 * k + 1] = 2.0f * z.y - 1.0f;
+            v[2 * k] = centered ? z.x : 2.0f * z.x - 1.0f;
+            v[2 * k + 1] = centered ? z.y : 2.0f * z.y - 1.0f;
         } else {
             v[2 * k] = 0.f; v[2 * k + 1] = 0.f;
         }
@@ -101,7 +102,7 @@ void input_pyramid_kernel(const pyr::InParams p) {
                 if (q < n0 && gy >= 0 && gy < H && gx >= 0 && gx < W) {
                     gpx[u] = (long long)gy * W + gx;
                     if constexpr (PACK) {
-                        pack_pixel(p.in, p.n_in, (long long)b * H * W + gpx[u], v[u]);
+                        pack_pixel(p.in, p.n_in, (long long)b * H * W + gpx[u], v[u], p.centered);
                         own[u] = gy >= oy0 && gy < oy1 && gx >= ox0 && gx < ox1;
                     } else {
                         load8(g0 + gpx[u] * 8, v[u]);
@@ -147,6 +148,41 @@ void input_pyramid_kernel(const pyr::InParams p) {
         }
         __syncthreads();
     }
+}
+
+// ---- the non-FIR input pyramid (fir=False: pyramid_downsample = avg_pool2d(2), layerspp.py:151-156): level k = the 2 x 2 mean of level k - 1,
+// ((x00 + x01) + (x10 + x11)) / 4 in fp32, every level rounded to the storage type (what a level-by-level chain would read back).  No halo:
+// a thread owns ONE pixel of the launch's coarsest level and the 2^nd x 2^nd block of level 0 under it, reduced depth first in registers;
+// it writes every pixel of every level it passes.  One launch for packing + up to three steps, like the FIR kernel above.
+template <typename T, bool PACK, int K>
+__device__ __forceinline__ void mean_node(const pyr::InParams& p, int b, int y, int x, float (&v)[8]) {
+    const int H = p.H >> K, W = p.W >> K;
+    T* const g = static_cast<T*>(p.lvl[K]) + ((long long)b * H * W + (long long)y * W + x) * 8;
+    if constexpr (K == 0) {
+        if constexpr (PACK) { pack_pixel(p.in, p.n_in, (long long)b * H * W + (long long)y * W + x, v, p.centered); store8(g, v); round8<T>(v); }
+        else load8(g, v);
+    } else {
+        float c[4][8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mean_node<T, PACK, K - 1>(p, b, 2 * y + (q >> 1), 2 * x + (q & 1), c[q]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = ((c[0][e] + c[1][e]) + (c[2][e] + c[3][e])) * 0.25f;
+        store8(g, v);
+        round8<T>(v);
+    }
+}
+template <typename T, bool PACK>
+__global__ __launch_bounds__(256)
+void input_pyramid_mean_kernel(const pyr::InParams p) {
+    const int nd = p.nd, Hc = p.H >> nd, Wc = p.W >> nd;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)p.B * Hc * Wc) return;
+    const int x = (int)(i % Wc), y = (int)((i / Wc) % Hc), b = (int)(i / ((long long)Wc * Hc));
+    float v[8];
+    if (nd == 0) mean_node<T, PACK, 0>(p, b, y, x, v);
+    else if (nd == 1) mean_node<T, PACK, 1>(p, b, y, x, v);
+    else if (nd == 2) mean_node<T, PACK, 2>(p, b, y, x, v);
+    else mean_node<T, PACK, 3>(p, b, y, x, v);
 }
 
 // ---- output pyramid + head: p_{nl-1} = ph_{nl-1}; p_k = T(up(p_{k+1}) + ph_k) (fir_kernel<T, 1> with its add operand: out[2i + a] =
@@ -242,8 +278,8 @@ using namespace storm;
 
 // levels[k] = [B][F >> k][T >> k][8] for k = 0 .. n_levels - 1.  cplx_in != NULL: level 0 is WRITTEN (the packed inputs, storm_pack_input);
 // cplx_in == NULL: level 0 is read (the continuation of a pyramid deeper than three steps).  At most pyr::MAXD + 1 levels per call.
-extern "C" int storm_input_pyramid(const float* const* cplx_in, int n_in, void* const* levels, int n_levels, int B, int F, int T, int dtype,
-                                   storm_stream_t s) {
+extern "C" int storm_input_pyramid_ex(const float* const* cplx_in, int n_in, void* const* levels, int n_levels, int B, int F, int T, int mean,
+                                      int centered, int dtype, storm_stream_t s) {
     STORM_CHECK(levels && n_levels >= 1 && n_levels <= pyr::MAXD + 1 && B > 0 && F > 0 && T > 0, "storm_input_pyramid: bad arguments (n_levels=%d)", n_levels);
     STORM_CHECK(cplx_in == nullptr || (n_in >= 1 && n_in <= 3), "storm_input_pyramid: n_in=%d", n_in);
     const int nd = n_levels - 1;
@@ -252,7 +288,21 @@ extern "C" int storm_input_pyramid(const float* const* cplx_in, int n_in, void* 
     memset(&p, 0, sizeof(p));
     for (int k = 0; k < n_levels; ++k) { STORM_CHECK(levels[k], "storm_input_pyramid: level %d is NULL", k); p.lvl[k] = levels[k]; }
     if (cplx_in) for (int i = 0; i < n_in; ++i) { STORM_CHECK(cplx_in[i], "storm_input_pyramid: null input %d", i); p.in[i] = cplx_in[i]; }
-    p.n_in = cplx_in ? n_in : 0; p.nd = nd; p.B = B; p.H = F; p.W = T;
+    p.n_in = cplx_in ? n_in : 0; p.nd = nd; p.B = B; p.H = F; p.W = T; p.centered = centered != 0;
+    if (mean) {                                                // fir=False: the 2 x 2 mean chain, one thread per pixel of the coarsest level
+        const long long n = (long long)B * (F >> nd) * (T >> nd);
+        STORM_CHECK((n + 255) / 256 < (1LL << 31), "storm_input_pyramid: grid out of range");
+        hipStream_t stm = (hipStream_t)s;
+#define STORM_IPM(T_) do { if (cplx_in) hipLaunchKernelGGL((input_pyramid_mean_kernel<T_, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stm, p); \
+        else hipLaunchKernelGGL((input_pyramid_mean_kernel<T_, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stm, p); } while (0)
+        if (dtype == STORM_BF16) STORM_IPM(bf16_t);
+        else if (dtype == STORM_F16) STORM_IPM(half_t);
+        else if (dtype == STORM_F32) STORM_IPM(float);
+        else STORM_CHECK(false, "storm_input_pyramid: dtype %d", dtype);
+#undef STORM_IPM
+        STORM_LAUNCH_CHECK();
+        return STORM_OK;
+    }
     // the coarsest level's tile: 4 x 8 pixels behind three steps, 8 x 16 behind two, 16 x 32 behind one (a level-0 region of <= 46 x 78 pixels)
     p.th = 32 >> nd; p.tw = 64 >> nd;
     const int Hc = F >> nd, Wc = T >> nd;
@@ -277,6 +327,11 @@ extern "C" int storm_input_pyramid(const float* const* cplx_in, int n_in, void* 
 #undef STORM_IP
     STORM_LAUNCH_CHECK();
     return STORM_OK;
+}
+
+extern "C" int storm_input_pyramid(const float* const* cplx_in, int n_in, void* const* levels, int n_levels, int B, int F, int T, int dtype,
+                                   storm_stream_t s) {
+    return storm_input_pyramid_ex(cplx_in, n_in, levels, n_levels, B, F, T, 0, 0, dtype, s);
 }
 
 // ph[k] = [B][F >> k][T >> k][8] (the narrow convolutions' outputs, finest first), n_levels <= 8; the rest as storm_output_head.

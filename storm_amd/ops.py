@@ -210,10 +210,11 @@ def gn_stats(xa, xb=None):
 
 
 def gn_apply(xa, stats, gamma, beta, xb=None, silu=True, resample=0, eps=1e-6, want_raw=True):
+    """resample: 0 none, 1 / 2 FIR x2 up / down, 3 / 4 the non-FIR members (nearest x2 up / 2x2 mean down, fir=False)"""
     B, H, W, Ca = xa.shape
     Cb = xb.shape[-1] if xb is not None else 0
     Ctot = Ca + Cb
-    OH, OW = (2 * H, 2 * W) if resample == 1 else ((H // 2, W // 2) if resample == 2 else (H, W))
+    OH, OW = (2 * H, 2 * W) if resample in (1, 3) else ((H // 2, W // 2) if resample in (2, 4) else (H, W))
     out = _alloc((B, OH, OW, Ctot), xa.dtype, xa)
     raw = _alloc((B, OH, OW, Ctot), xa.dtype, xa) if (resample and want_raw) else None
     L.check(L.lib().storm_gn_apply(L.ptr(xa), Ca, L.ptr(xb), Cb, B, H, W, stats.shape[1], L.ptr(stats),
