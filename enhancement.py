@@ -4,10 +4,11 @@
     python enhancement.py --test_dir noisy/ --enhanced_dir out/ --ckpt model.ckpt --mode storm \
         [--corrector ald --corrector-steps 1 --snr 0.5 --N 50]
 
-Additions: --precision {fp32,bf16}, --batch (equal-length utterances per sampler call), --seed and multi-GPU
+Additions: --precision {fp32,bf16}, --batch (equal-length utterances per sampler call), --seed / --utterance-seed and multi-GPU
 sharding when launched with torchrun (one process per GPU, files dealt by length; no collectives in the
 sampler).  WAV I/O uses scipy.io.wavfile (torchaudio is not required)."""
 import glob
+import hashlib
 import os
 from argparse import ArgumentParser
 
@@ -35,6 +36,11 @@ def write_wav(path, x, sr):
     wavfile.write(path, sr, x.detach().cpu().numpy().astype(np.float32))
 
 
+def utterance_key(seed, path):
+    """--utterance-seed: a file's Philox key from the seed and its NAME only, (S + first 8 bytes of sha256(basename), little endian) mod 2^63"""
+    return (seed + int.from_bytes(hashlib.sha256(os.path.basename(path).encode()).digest()[:8], "little")) % 2 ** 63
+
+
 def main():
     p = ArgumentParser()
     p.add_argument("--test_dir", type=str, required=True, help="Directory containing your corrupted files to enhance.")
@@ -50,12 +56,17 @@ def main():
     p.add_argument("--precision", choices=("fp32", "bf16", "fp16"), default="fp32")
     p.add_argument("--batch", type=int, default=16)
     p.add_argument("--seed", type=int, default=None, help="Philox seed of the sampler noise (default: drawn from torch's RNG, as the reference)")
+    p.add_argument("--utterance-seed", type=int, default=None, help="instead of --seed: every file draws from a Philox key of its own, formed from this seed and the file's "
+                   "name, so its enhanced wav depends only on (seed, name, samples, precision) - not on the other files of --test_dir, nor on --batch, --group or "
+                   "the number of GPUs.  fp32: equal to rounding; bit for bit (and in bf16 / fp16 at all) only together with --batch-invariant")
     p.add_argument("--batch-invariant", action="store_true", help="every utterance's result independent - bit for bit - of what it is batched with "
                    "(storm_amd.set_batch_invariant: launch decisions per image; costs the batch-aware kernel selections)")
     p.add_argument("--group", type=int, default=8, help="score-only and storm modes: this many micro-batches (frame buckets of different lengths) run their samplers in lockstep "
                    "and share the launches of the score network (ScoreModel.enhance_stream); 1 = one micro-batch after the other")
     p.add_argument("--dist-world1", action="store_true", help="with ONE rank: form the RCCL process group anyway (dry run of the sharded path on one GPU)")
     args = p.parse_args()
+    if args.seed is not None and args.utterance_seed is not None:
+        raise SystemExit("--seed and --utterance-seed exclude each other")
     if args.sampler == "ode" and args.mode != "score-only":
         raise SystemExit("--sampler ode: score-only mode (the reference's StoRM ODE path drops the conditioning, model.py:671-691)")
 
@@ -96,11 +107,14 @@ def main():
             outs = [model.enhance(wavs[i]) for i in ids]
         else:
             kw = {} if args.seed is None else dict(seed=args.seed + ids[0])     # distinct, reproducible draws per batch
+            if args.utterance_seed is not None:
+                kw = dict(row_seeds=[keys[i] for i in ids])                     # every file its own draws, whatever it is batched with
             x_hat = model.enhance_batch(y, lengths=ragged, **skw, **kw)
             outs = [x_hat[k, :lens[k]] for k in range(len(ids))]
         return ids, outs
 
     skw = dict(sampler_type="ode", N=args.N) if args.sampler == "ode" else dict(corrector=args.corrector, N=args.N, corrector_steps=args.corrector_steps, snr=args.snr)
+    keys = None if args.utterance_seed is None else [utterance_key(args.utterance_seed, f) for f in files]
     buckets = D.bucket_by_frames([lengths[i] for i in mine], args.batch)
     if args.mode in ("score-only", "storm") and args.group > 1 and len(buckets) > 1:
         # a ragged set of files: micro-batches of 2 - 3 rows each - their score evaluations share launches (storm_ncsnpp_forward_group)
@@ -115,7 +129,7 @@ def main():
             chunk.append((y, None if len(set(lens)) == 1 else lens))
             metas.append((ids, lens))
         outs = model.enhance_stream(chunk, width=args.group, seeds=None if args.seed is None else [args.seed + ids[0] for ids, _ in metas],     # (the draws of the one-by-one path)
-                                    **skw)
+                                    row_seeds=None if keys is None else [[keys[i] for i in ids] for ids, _ in metas], **skw)
         for (ids, lens), x_hat in zip(metas, outs):
             for k, i in enumerate(ids):
                 write_wav(os.path.join(args.enhanced_dir, os.path.basename(files[i])), x_hat[k, :lens[k]].float().reshape(-1), 16000)

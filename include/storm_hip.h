@@ -298,6 +298,28 @@ int storm_ouve_predictor_step(float* x, float* x_mean, const float* score, const
                               const float* z, const float* t, int B, long long n, storm_ouve p,
                               int kind, int noise_free, uint64_t seed, uint64_t offset,
                               storm_stream_t s);
+/* ---- per-row noise keys (the *_rs forms).  The entry points above draw element i of row b from the Philox counter b * n + i of ONE
+ * seed: a row's noise depends on where it sits in the batch.  The *_rs forms take their sibling's argument list plus
+ * row_seeds = device uint64 [B] and draw row b from (key row_seeds[b], counter i within the row, offset) - exactly what the
+ * sibling called on that row alone (B = 1) with seed = row_seeds[b] and the same offset draws, so a seeded result does not depend on
+ * the batch around it.  `seed` is not read; z != NULL injects noise as before; everything after the draw is the sibling's arithmetic.
+ * They replace the same reference lines as their siblings, called once per utterance (enhancement.py:66-72: one file per call):
+ *   storm_ouve_prior_rs              OUVESDE.prior_sampling (sdes.py:233-237)
+ *   storm_ouve_ald_step_rs           AnnealedLangevinDynamics.update_fn (correctors.py:64-93)
+ *   storm_ouve_predictor_step_rs     ReverseDiffusionPredictor / EulerMaruyamaPredictor.update_fn (predictors.py:46-69) with
+ *                                    SDE.discretize / RSDE.discretize (sdes.py:73-90, 147-157)
+ *   storm_sde_prior_rows_rs          OUVPSDE.prior_sampling (sdes.py:306-310)
+ *   storm_sde_predictor_step_rows_rs the predictors' update_fn (predictors.py:46-69) over OUVPSDE (sdes.py:286-301, 123-157)
+ *   storm_complex_randn_rs           torch.randn_like(x) of LangevinCorrector.update_fn (correctors.py:50-52): z = [B][n_per_row] */
+int storm_ouve_prior_rs(const float* y, const float* z, float* x, int B, long long n, storm_ouve p,
+                        uint64_t seed, uint64_t offset, const uint64_t* row_seeds, storm_stream_t s);
+int storm_ouve_ald_step_rs(float* x, float* x_mean, const float* score, const float* z, const float* t,
+                           int B, long long n, storm_ouve p, float snr,
+                           uint64_t seed, uint64_t offset, const uint64_t* row_seeds, storm_stream_t s);
+int storm_ouve_predictor_step_rs(float* x, float* x_mean, const float* score, const float* y,
+                                 const float* z, const float* t, int B, long long n, storm_ouve p,
+                                 int kind, int noise_free, uint64_t seed, uint64_t offset,
+                                 const uint64_t* row_seeds, storm_stream_t s);
 /* per-batch L2 norms of complex tensors: out[b] = ||v_b||  (correctors.py:53-54) */
 int storm_batch_l2norm(const float* v, float* out, int B, long long n, storm_stream_t s);
 /* Langevin corrector step; z must be given or generated beforehand (its norm is needed):
@@ -330,6 +352,13 @@ int storm_sde_prior_rows(const float* y, const float* z, float* x, const float* 
 int storm_sde_predictor_step_rows(float* x, float* x_mean, const float* score, const float* y, const float* z,
                                   const float* a_rows, const float* g_rows, int B, long long n, int N, int kind,
                                   int noise_free, uint64_t seed, uint64_t offset, storm_stream_t s);
+/* the same two with per-row noise keys (see storm_ouve_prior_rs) */
+int storm_sde_prior_rows_rs(const float* y, const float* z, float* x, const float* std_rows, int B, long long n,
+                            uint64_t seed, uint64_t offset, const uint64_t* row_seeds, storm_stream_t s);
+int storm_sde_predictor_step_rows_rs(float* x, float* x_mean, const float* score, const float* y, const float* z,
+                                     const float* a_rows, const float* g_rows, int B, long long n, int N, int kind,
+                                     int noise_free, uint64_t seed, uint64_t offset, const uint64_t* row_seeds,
+                                     storm_stream_t s);
 /* out = a_b (y - x) - 1/2 g_b^2 score: the probability-flow right-hand side (sdes.py:92-145 with probability_flow=True) */
 int storm_sde_pf_drift_rows(float* out, const float* x, const float* y, const float* score, const float* a_rows,
                             const float* g_rows, int B, long long n, storm_stream_t s);
@@ -363,6 +392,10 @@ int storm_copy_rows(void* dst, const void* src, const int* row_mask, int B, long
 /* fills z[B*n] complex with standard complex normal noise (Philox) */
 int storm_complex_randn(float* z, long long n_complex, uint64_t seed, uint64_t offset,
                         storm_stream_t s);
+/* rows form: z[B][n_per_row], row b = storm_complex_randn(n_per_row, row_seeds[b], offset) (see storm_ouve_prior_rs; the draw
+ * of torch.randn_like in LangevinCorrector.update_fn, correctors.py:50-52, made per utterance) */
+int storm_complex_randn_rs(float* z, int B, long long n_per_row, uint64_t seed, uint64_t offset,
+                           const uint64_t* row_seeds, storm_stream_t s);
 
 /* ------------------------------------------------------------------------------------------
  * Spectral front / back end.  Replace torch.stft / torch.istft as called by

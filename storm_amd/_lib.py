@@ -109,6 +109,9 @@ _SIGNATURES = {
     "storm_ouve_prior": ([_vp, _vp, _vp, _i, _ll, Ouve, _u64, _u64, _vp], C.c_int),
     "storm_ouve_ald_step": ([_vp, _vp, _vp, _vp, _vp, _i, _ll, Ouve, _f, _u64, _u64, _vp], C.c_int),
     "storm_ouve_predictor_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, Ouve, _i, _i, _u64, _u64, _vp], C.c_int),
+    "storm_ouve_prior_rs": ([_vp, _vp, _vp, _i, _ll, Ouve, _u64, _u64, _vp, _vp], C.c_int),
+    "storm_ouve_ald_step_rs": ([_vp, _vp, _vp, _vp, _vp, _i, _ll, Ouve, _f, _u64, _u64, _vp, _vp], C.c_int),
+    "storm_ouve_predictor_step_rs": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, Ouve, _i, _i, _u64, _u64, _vp, _vp], C.c_int),
     "storm_batch_l2norm": ([_vp, _vp, _i, _ll, _vp], C.c_int),
     "storm_langevin_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _f, _i, _vp], C.c_int),
     "storm_si_sdr": ([_vp, _vp, _vp, _i, _ll, _ll, _ll, _f, _vp], C.c_int),
@@ -116,6 +119,8 @@ _SIGNATURES = {
     "storm_ouve_pf_drift_g": ([_vp, _vp, _vp, _vp, _vp, _i, _ll, _f, _vp], C.c_int),
     "storm_sde_prior_rows": ([_vp, _vp, _vp, _vp, _i, _ll, _u64, _u64, _vp], C.c_int),
     "storm_sde_predictor_step_rows": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _u64, _u64, _vp], C.c_int),
+    "storm_sde_prior_rows_rs": ([_vp, _vp, _vp, _vp, _i, _ll, _u64, _u64, _vp, _vp], C.c_int),
+    "storm_sde_predictor_step_rows_rs": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _u64, _u64, _vp, _vp], C.c_int),
     "storm_sde_pf_drift_rows": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _vp], C.c_int),
     "storm_rk_combine": ([_vp, _vp, C.POINTER(_vp), C.POINTER(C.c_float), _i, _f, _ll, _vp], C.c_int),
     "storm_rk_scaled_sumsq": ([_vp, _vp, _i, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_float), _i, _f, _f, _f, _ll, _vp], C.c_int),
@@ -123,6 +128,7 @@ _SIGNATURES = {
     "storm_rk_scaled_sumsq_rows": ([_vp, _vp, _ll, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_double), _i, C.POINTER(C.c_double), C.c_double, C.c_double, _i, _ll, _vp], C.c_int),
     "storm_copy_rows": ([_vp, _vp, C.POINTER(C.c_int), _i, _ll, _vp], C.c_int),
     "storm_complex_randn": ([_vp, _ll, _u64, _u64, _vp], C.c_int),
+    "storm_complex_randn_rs": ([_vp, _i, _ll, _u64, _u64, _vp, _vp], C.c_int),
     "storm_spec_transform": ([_vp, _vp, _ll, _f, _f, _i, _vp], C.c_int),
     "storm_peak_abs": ([_vp, _vp, _i, _ll, _ll, _vp, _vp], C.c_int),
     "storm_stft": ([_vp, _vp, _vp, _vp, _vp, _i, _ll, _ll, _i, _i, _i, _i, _f, _f, _vp, _vp], C.c_int),

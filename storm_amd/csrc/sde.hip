@@ -30,8 +30,21 @@ __device__ inline float2 complex_normal(uint64_t seed, uint64_t idx, uint64_t of
     sincosf(6.28318530717958647692f * u2, &sn, &cs);
     return make_float2(r * cs, r * sn);
 }
-__device__ inline float2 get_noise(const float* z, long long i, uint64_t seed, uint64_t offset) {
-    return z ? reinterpret_cast<const float2*>(z)[i] : complex_normal(seed, (uint64_t)i, offset);
+// Where a generated draw takes its Philox key and counter from.  BatchKey: one seed for the whole call, the counter is the
+// element's position in the BATCH (k = b * n + i).  RowKeys: row b has its own key row_seeds[b] and counts from 0 within the
+// row, so the row draws what a batch-1 call with seed = row_seeds[b] draws (there b = 0 and k = i) wherever it sits in a batch.
+struct BatchKey {
+    uint64_t seed;
+    __device__ float2 draw(int, long long, long long k, uint64_t offset) const { return complex_normal(seed, (uint64_t)k, offset); }
+};
+struct RowKeys {
+    const uint64_t* row_seeds;                     // device [B]
+    __device__ float2 draw(int b, long long i, long long, uint64_t offset) const { return complex_normal(row_seeds[b], (uint64_t)i, offset); }
+};
+// injected noise z (batch layout) or a generated draw for element i of row b (k = b * n + i)
+template <class Key>
+__device__ inline float2 get_noise(const float* z, int b, long long i, long long k, Key key, uint64_t offset) {
+    return z ? reinterpret_cast<const float2*>(z)[k] : key.draw(b, i, k, offset);
 }
 
 // ---- OUVE coefficient helpers (sdes.py:200-231), fp64 then rounded ---------------------------
@@ -49,21 +62,23 @@ __device__ inline float ouve_g(const Ouve& o, double t) {
     return (float)(o.smin * pow(o.smax / o.smin, t) * sqrt(2.0 * o.logsig));
 }
 
+template <class Key>
 __global__ void ouve_prior_kernel(const float* __restrict__ y, const float* __restrict__ z, float* __restrict__ x,
-                                  long long n, storm_ouve p, uint64_t seed, uint64_t offset) {
+                                  long long n, storm_ouve p, Key key, uint64_t offset) {
     const int b = blockIdx.y;
     const float std1 = ouve_std(make_ouve(p), 1.0);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const long long k = (long long)b * n + i;
         const float2 yy = reinterpret_cast<const float2*>(y)[k];
-        const float2 zz = get_noise(z, k, seed, offset);
+        const float2 zz = get_noise(z, b, i, k, key, offset);
         reinterpret_cast<float2*>(x)[k] = make_float2(yy.x + zz.x * std1, yy.y + zz.y * std1);
     }
 }
 
+template <class Key>
 __global__ void ouve_ald_kernel(float* __restrict__ x, float* __restrict__ x_mean, const float* __restrict__ score,
                                 const float* __restrict__ z, const float* __restrict__ t, long long n, storm_ouve p,
-                                float snr, uint64_t seed, uint64_t offset) {
+                                float snr, Key key, uint64_t offset) {
     const int b = blockIdx.y;
     const float std = ouve_std(make_ouve(p), (double)t[b]);
     const float sstd = snr * std;
@@ -73,17 +88,18 @@ __global__ void ouve_ald_kernel(float* __restrict__ x, float* __restrict__ x_mea
         const long long k = (long long)b * n + i;
         const float2 xx = reinterpret_cast<const float2*>(x)[k];
         const float2 s = reinterpret_cast<const float2*>(score)[k];
-        const float2 zz = get_noise(z, k, seed, offset);
+        const float2 zz = get_noise(z, b, i, k, key, offset);
         const float2 xm = make_float2(xx.x + step * s.x, xx.y + step * s.y);
         if (x_mean) reinterpret_cast<float2*>(x_mean)[k] = xm;
         reinterpret_cast<float2*>(x)[k] = make_float2(xm.x + zz.x * nscale, xm.y + zz.y * nscale);
     }
 }
 
+template <class Key>
 __global__ void ouve_predictor_kernel(float* __restrict__ x, float* __restrict__ x_mean, const float* __restrict__ score,
                                       const float* __restrict__ y, const float* __restrict__ z,
                                       const float* __restrict__ t, long long n, storm_ouve p, int kind,
-                                      int noise_free, uint64_t seed, uint64_t offset) {
+                                      int noise_free, Key key, uint64_t offset) {
     const int b = blockIdx.y;
     const Ouve o = make_ouve(p);
     const float g = ouve_g(o, (double)t[b]);
@@ -112,7 +128,7 @@ __global__ void ouve_predictor_kernel(float* __restrict__ x, float* __restrict__
         if (noise_free) {
             reinterpret_cast<float2*>(x)[k] = xm;
         } else {
-            const float2 zz = get_noise(z, k, seed, offset);
+            const float2 zz = get_noise(z, b, i, k, key, offset);
             reinterpret_cast<float2*>(x)[k] = make_float2(xm.x + G * zz.x, xm.y + G * zz.y);
         }
     }
@@ -161,9 +177,14 @@ __global__ void langevin_kernel(float* __restrict__ x, float* __restrict__ x_mea
     }
 }
 
-__global__ void complex_randn_kernel(float* __restrict__ z, long long n, uint64_t seed, uint64_t offset) {
-    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x)
-        reinterpret_cast<float2*>(z)[k] = complex_normal(seed, (uint64_t)k, offset);
+// z[b][i], n values per row, one row per grid.y (the one-seed form is launched as ONE row holding all the values: k = i there)
+template <class Key>
+__global__ void complex_randn_kernel(float* __restrict__ z, long long n, Key key, uint64_t offset) {
+    const int b = blockIdx.y;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long k = (long long)b * n + i;
+        reinterpret_cast<float2*>(z)[k] = key.draw(b, i, k, offset);
+    }
 }
 
 // drift of the probability-flow ODE: theta (y - x) - 1/2 g(t)^2 score  (sdes.py:92-121 with probability_flow=True, :203-207)
@@ -205,22 +226,24 @@ __global__ void ouve_pf_drift_g_kernel(float* __restrict__ out, const float* __r
 // g = sqrt(beta(t))).  The caller hands a(t_b), g(t_b), std(t_b) per row (device fp32 [B]) in the reference's own fp32 torch
 // expressions; the state update is the OUVE kernels' (same op order: SDE.discretize sdes.py:86-90, RSDE.discretize :147-157,
 // rsde_parts :123-145, predictors.py:46-69). -------------------------------------------------------------------------------------
+template <class Key>
 __global__ void sde_prior_rows_kernel(const float* __restrict__ y, const float* __restrict__ z, float* __restrict__ x,
-                                      const float* __restrict__ std_rows, long long n, uint64_t seed, uint64_t offset) {
+                                      const float* __restrict__ std_rows, long long n, Key key, uint64_t offset) {
     const int b = blockIdx.y;
     const float sd = std_rows[b];
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const long long k = (long long)b * n + i;
         const float2 yy = reinterpret_cast<const float2*>(y)[k];
-        const float2 zz = get_noise(z, k, seed, offset);
+        const float2 zz = get_noise(z, b, i, k, key, offset);
         reinterpret_cast<float2*>(x)[k] = make_float2(yy.x + zz.x * sd, yy.y + zz.y * sd);
     }
 }
 
+template <class Key>
 __global__ void sde_predictor_rows_kernel(float* __restrict__ x, float* __restrict__ x_mean, const float* __restrict__ score,
                                           const float* __restrict__ y, const float* __restrict__ z, const float* __restrict__ a_rows,
                                           const float* __restrict__ g_rows, long long n, int N, int kind, int noise_free,
-                                          uint64_t seed, uint64_t offset) {
+                                          Key key, uint64_t offset) {
     const int b = blockIdx.y;
     const float a = a_rows[b], g = g_rows[b];
     const float dt = (float)(1.0 / N);
@@ -243,7 +266,7 @@ __global__ void sde_predictor_rows_kernel(float* __restrict__ x, float* __restri
         if (noise_free) {
             reinterpret_cast<float2*>(x)[k] = xm;
         } else {
-            const float2 zz = get_noise(z, k, seed, offset);
+            const float2 zz = get_noise(z, b, i, k, key, offset);
             reinterpret_cast<float2*>(x)[k] = make_float2(xm.x + G * zz.x, xm.y + G * zz.y);
         }
     }
@@ -419,31 +442,69 @@ static inline int ew_blocks(long long n) { long long b = (n + 255) / 256; return
 
 using namespace storm;
 
-extern "C" int storm_ouve_prior(const float* y, const float* z, float* x, int B, long long n, storm_ouve p,
-                                uint64_t seed, uint64_t offset, storm_stream_t s) {
-    STORM_CHECK(y && x && B > 0 && n > 0, "storm_ouve_prior: bad arguments");
-    hipLaunchKernelGGL(ouve_prior_kernel, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, y, z, x, n, p, seed, offset);
+// Every entry point that can generate noise exists twice - one seed for the call (BatchKey) or a key per row (RowKeys, the *_rs
+// names; their `seed` argument is not read) - around ONE launch function templated on the key.
+template <class Key>
+static int launch_ouve_prior(const char* who, const float* y, const float* z, float* x, int B, long long n, storm_ouve p, Key key,
+                             uint64_t offset, storm_stream_t s) {
+    STORM_CHECK(y && x && B > 0 && n > 0, "%s: bad arguments", who);
+    hipLaunchKernelGGL(ouve_prior_kernel<Key>, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, y, z, x, n, p, key, offset);
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }
+extern "C" int storm_ouve_prior(const float* y, const float* z, float* x, int B, long long n, storm_ouve p,
+                                uint64_t seed, uint64_t offset, storm_stream_t s) {
+    return launch_ouve_prior("storm_ouve_prior", y, z, x, B, n, p, BatchKey{seed}, offset, s);
+}
+extern "C" int storm_ouve_prior_rs(const float* y, const float* z, float* x, int B, long long n, storm_ouve p,
+                                   uint64_t seed, uint64_t offset, const uint64_t* row_seeds, storm_stream_t s) {
+    (void)seed;
+    STORM_CHECK(row_seeds, "storm_ouve_prior_rs: null row_seeds");
+    return launch_ouve_prior("storm_ouve_prior_rs", y, z, x, B, n, p, RowKeys{row_seeds}, offset, s);
+}
 
+template <class Key>
+static int launch_ouve_ald(const char* who, float* x, float* x_mean, const float* score, const float* z, const float* t, int B,
+                           long long n, storm_ouve p, float snr, Key key, uint64_t offset, storm_stream_t s) {
+    STORM_CHECK(x && score && t && B > 0 && n > 0, "%s: bad arguments", who);
+    hipLaunchKernelGGL(ouve_ald_kernel<Key>, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, x, x_mean, score, z, t, n, p, snr, key, offset);
+    STORM_LAUNCH_CHECK();
+    return STORM_OK;
+}
 extern "C" int storm_ouve_ald_step(float* x, float* x_mean, const float* score, const float* z, const float* t, int B,
                                    long long n, storm_ouve p, float snr, uint64_t seed, uint64_t offset,
                                    storm_stream_t s) {
-    STORM_CHECK(x && score && t && B > 0 && n > 0, "storm_ouve_ald_step: bad arguments");
-    hipLaunchKernelGGL(ouve_ald_kernel, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, x, x_mean, score, z, t, n, p, snr, seed, offset);
+    return launch_ouve_ald("storm_ouve_ald_step", x, x_mean, score, z, t, B, n, p, snr, BatchKey{seed}, offset, s);
+}
+extern "C" int storm_ouve_ald_step_rs(float* x, float* x_mean, const float* score, const float* z, const float* t, int B,
+                                      long long n, storm_ouve p, float snr, uint64_t seed, uint64_t offset,
+                                      const uint64_t* row_seeds, storm_stream_t s) {
+    (void)seed;
+    STORM_CHECK(row_seeds, "storm_ouve_ald_step_rs: null row_seeds");
+    return launch_ouve_ald("storm_ouve_ald_step_rs", x, x_mean, score, z, t, B, n, p, snr, RowKeys{row_seeds}, offset, s);
+}
+
+template <class Key>
+static int launch_ouve_predictor(const char* who, float* x, float* x_mean, const float* score, const float* y, const float* z,
+                                 const float* t, int B, long long n, storm_ouve p, int kind, int noise_free, Key key, uint64_t offset,
+                                 storm_stream_t s) {
+    STORM_CHECK(x && score && y && t && B > 0 && n > 0 && p.N > 0, "%s: bad arguments", who);
+    STORM_CHECK(kind == 0 || kind == 1, "%s: kind=%d", who, kind);
+    hipLaunchKernelGGL(ouve_predictor_kernel<Key>, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, x, x_mean, score, y, z, t, n, p, kind, noise_free, key, offset);
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }
-
 extern "C" int storm_ouve_predictor_step(float* x, float* x_mean, const float* score, const float* y, const float* z,
                                          const float* t, int B, long long n, storm_ouve p, int kind, int noise_free,
                                          uint64_t seed, uint64_t offset, storm_stream_t s) {
-    STORM_CHECK(x && score && y && t && B > 0 && n > 0 && p.N > 0, "storm_ouve_predictor_step: bad arguments");
-    STORM_CHECK(kind == 0 || kind == 1, "storm_ouve_predictor_step: kind=%d", kind);
-    hipLaunchKernelGGL(ouve_predictor_kernel, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, x, x_mean, score, y, z, t, n, p, kind, noise_free, seed, offset);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
+    return launch_ouve_predictor("storm_ouve_predictor_step", x, x_mean, score, y, z, t, B, n, p, kind, noise_free, BatchKey{seed}, offset, s);
+}
+extern "C" int storm_ouve_predictor_step_rs(float* x, float* x_mean, const float* score, const float* y, const float* z,
+                                            const float* t, int B, long long n, storm_ouve p, int kind, int noise_free,
+                                            uint64_t seed, uint64_t offset, const uint64_t* row_seeds, storm_stream_t s) {
+    (void)seed;
+    STORM_CHECK(row_seeds, "storm_ouve_predictor_step_rs: null row_seeds");
+    return launch_ouve_predictor("storm_ouve_predictor_step_rs", x, x_mean, score, y, z, t, B, n, p, kind, noise_free, RowKeys{row_seeds}, offset, s);
 }
 
 extern "C" int storm_batch_l2norm(const float* v, float* out, int B, long long n, storm_stream_t s) {
@@ -464,7 +525,15 @@ extern "C" int storm_langevin_step(float* x, float* x_mean, const float* score, 
 
 extern "C" int storm_complex_randn(float* z, long long n_complex, uint64_t seed, uint64_t offset, storm_stream_t s) {
     STORM_CHECK(z && n_complex > 0, "storm_complex_randn: bad arguments");
-    hipLaunchKernelGGL(complex_randn_kernel, dim3(ew_blocks(n_complex)), dim3(256), 0, (hipStream_t)s, z, n_complex, seed, offset);
+    hipLaunchKernelGGL(complex_randn_kernel<BatchKey>, dim3(ew_blocks(n_complex)), dim3(256), 0, (hipStream_t)s, z, n_complex, BatchKey{seed}, offset);
+    STORM_LAUNCH_CHECK();
+    return STORM_OK;
+}
+extern "C" int storm_complex_randn_rs(float* z, int B, long long n_per_row, uint64_t seed, uint64_t offset,
+                                      const uint64_t* row_seeds, storm_stream_t s) {
+    (void)seed;
+    STORM_CHECK(z && B > 0 && n_per_row > 0 && row_seeds, "storm_complex_randn_rs: bad arguments");
+    hipLaunchKernelGGL(complex_randn_kernel<RowKeys>, dim3(ew_blocks(n_per_row), B), dim3(256), 0, (hipStream_t)s, z, n_per_row, RowKeys{row_seeds}, offset);
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }
@@ -575,23 +644,50 @@ extern "C" int storm_ouve_pf_drift_g(float* out, const float* x, const float* y,
     return STORM_OK;
 }
 
-extern "C" int storm_sde_prior_rows(const float* y, const float* z, float* x, const float* std_rows, int B, long long n,
-                                    uint64_t seed, uint64_t offset, storm_stream_t s) {
-    STORM_CHECK(y && x && std_rows && B > 0 && n > 0, "storm_sde_prior_rows: bad arguments");
-    hipLaunchKernelGGL(sde_prior_rows_kernel, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, y, z, x, std_rows, n, seed, offset);
+template <class Key>
+static int launch_sde_prior_rows(const char* who, const float* y, const float* z, float* x, const float* std_rows, int B, long long n,
+                                 Key key, uint64_t offset, storm_stream_t s) {
+    STORM_CHECK(y && x && std_rows && B > 0 && n > 0, "%s: bad arguments", who);
+    hipLaunchKernelGGL(sde_prior_rows_kernel<Key>, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, y, z, x, std_rows, n, key, offset);
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }
+extern "C" int storm_sde_prior_rows(const float* y, const float* z, float* x, const float* std_rows, int B, long long n,
+                                    uint64_t seed, uint64_t offset, storm_stream_t s) {
+    return launch_sde_prior_rows("storm_sde_prior_rows", y, z, x, std_rows, B, n, BatchKey{seed}, offset, s);
+}
+extern "C" int storm_sde_prior_rows_rs(const float* y, const float* z, float* x, const float* std_rows, int B, long long n,
+                                       uint64_t seed, uint64_t offset, const uint64_t* row_seeds, storm_stream_t s) {
+    (void)seed;
+    STORM_CHECK(row_seeds, "storm_sde_prior_rows_rs: null row_seeds");
+    return launch_sde_prior_rows("storm_sde_prior_rows_rs", y, z, x, std_rows, B, n, RowKeys{row_seeds}, offset, s);
+}
 
+template <class Key>
+static int launch_sde_predictor_rows(const char* who, float* x, float* x_mean, const float* score, const float* y, const float* z,
+                                     const float* a_rows, const float* g_rows, int B, long long n, int N, int kind, int noise_free,
+                                     Key key, uint64_t offset, storm_stream_t s) {
+    STORM_CHECK(x && score && y && a_rows && g_rows && B > 0 && n > 0 && N > 0, "%s: bad arguments", who);
+    STORM_CHECK(kind == 0 || kind == 1, "%s: kind=%d", who, kind);
+    hipLaunchKernelGGL(sde_predictor_rows_kernel<Key>, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, x, x_mean, score, y, z, a_rows, g_rows, n, N, kind,
+                       noise_free, key, offset);
+    STORM_LAUNCH_CHECK();
+    return STORM_OK;
+}
 extern "C" int storm_sde_predictor_step_rows(float* x, float* x_mean, const float* score, const float* y, const float* z,
                                              const float* a_rows, const float* g_rows, int B, long long n, int N, int kind,
                                              int noise_free, uint64_t seed, uint64_t offset, storm_stream_t s) {
-    STORM_CHECK(x && score && y && a_rows && g_rows && B > 0 && n > 0 && N > 0, "storm_sde_predictor_step_rows: bad arguments");
-    STORM_CHECK(kind == 0 || kind == 1, "storm_sde_predictor_step_rows: kind=%d", kind);
-    hipLaunchKernelGGL(sde_predictor_rows_kernel, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, x, x_mean, score, y, z, a_rows, g_rows, n, N, kind,
-                       noise_free, seed, offset);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
+    return launch_sde_predictor_rows("storm_sde_predictor_step_rows", x, x_mean, score, y, z, a_rows, g_rows, B, n, N, kind, noise_free,
+                                     BatchKey{seed}, offset, s);
+}
+extern "C" int storm_sde_predictor_step_rows_rs(float* x, float* x_mean, const float* score, const float* y, const float* z,
+                                                const float* a_rows, const float* g_rows, int B, long long n, int N, int kind,
+                                                int noise_free, uint64_t seed, uint64_t offset, const uint64_t* row_seeds,
+                                                storm_stream_t s) {
+    (void)seed;
+    STORM_CHECK(row_seeds, "storm_sde_predictor_step_rows_rs: null row_seeds");
+    return launch_sde_predictor_rows("storm_sde_predictor_step_rows_rs", x, x_mean, score, y, z, a_rows, g_rows, B, n, N, kind, noise_free,
+                                     RowKeys{row_seeds}, offset, s);
 }
 
 extern "C" int storm_sde_pf_drift_rows(float* out, const float* x, const float* y, const float* score, const float* a_rows,

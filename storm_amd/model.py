@@ -5,7 +5,7 @@ DiscriminativeModel :320, StochasticRegenerationModel :392) without Lightning: `
 ``eval(no_ema=False)`` EMA swap and ``load_from_checkpoint``.  Training methods are out of scope.
 
 New surface (not in the reference): ``enhance_batch`` (several utterances per call, equal to
-per-utterance ``enhance`` calls), ``set_precision`` and the ``noise_fn`` / ``seed`` sampler knobs.
+per-utterance ``enhance`` calls), ``set_precision`` and the ``noise_fn`` / ``seed`` / ``row_seeds`` sampler knobs.
 """
 import time
 import warnings
@@ -174,17 +174,25 @@ class _Base(nn.Module):
         """the network whose evaluations a grouped stream shares (ScoreModel: dnn; StoRM: score_net - its denoiser runs once per micro-batch)"""
         return getattr(self, "score_net", None) or self.dnn
 
-    def enhance_stream(self, batches, grouped=True, return_nfe=False, seed=None, seeds=None, noise_fns=None, width=None, **kwargs):
+    def enhance_stream(self, batches, grouped=True, return_nfe=False, seed=None, seeds=None, noise_fns=None, width=None, row_seeds=None,
+                       **kwargs):
         """(ScoreModel and StochasticRegenerationModel.)  A stream of ragged micro-batches (BASELINE.json configs[4]) in lockstep: `batches` = [(y [b, L], lengths or None), ...] as
         storm_amd.distributed.bucket_by_frames forms them.  Every micro-batch runs enhance_batch - the same sampler, noise stream and
         (ODE) per-row step control as its own call - but the score evaluations of all micro-batches that are still running share ONE
         grouped network call per step (storm_amd.sampling.grouped, storm_ncsnpp_forward_group): the layers with a grouped kernel see
         the whole stream's pixel tiles in one launch instead of 2 - 3 rows at a time.  grouped=False: one micro-batch after the other.
         seed: micro-batch k draws from the Philox stream seed + k (seeds: one seed per micro-batch; noise_fns: one injected-noise callable per micro-batch instead).
+        row_seeds: one list of per-row Philox keys per micro-batch (enhance_batch's row_seeds) instead of seed / seeds / noise_fns: every
+        utterance draws what its own batch-1 run with that key draws, whatever micro-batch it is in.
         width: at most this many micro-batches in flight (None = all); a finished one is replaced by the next of the list (storm_amd.sampling.grouped.run_grouped).
         Returns the list of enhanced batches (and the mean evaluations per utterance with return_nfe); self.last_nfev_stream = the
         evaluations every micro-batch executed."""
         from .sampling.grouped import run_grouped
+        if row_seeds is not None:
+            if seed is not None or seeds is not None or noise_fns is not None:
+                raise ValueError("row_seeds cannot be combined with seed, seeds or noise_fns")
+            if len(row_seeds) != len(batches):
+                raise ValueError(f"row_seeds has {len(row_seeds)} key lists for {len(batches)} micro-batches")
         outs = [None] * len(batches)
 
         def one(k):
@@ -196,6 +204,8 @@ class _Base(nn.Module):
                 kw["seed"] = seed + k
             if noise_fns is not None:
                 kw["noise_fn"] = noise_fns[k]                  # (parity runs: the draws of micro-batch k)
+            if row_seeds is not None:
+                kw["row_seeds"] = row_seeds[k]
             return self.enhance_batch(yb, lengths=bl, return_nfe=True, **kw)
         fns = [(lambda k=k: one(k)) for k in range(len(batches))]
         res, batcher = run_grouped(self._score_network(), fns, device=self.device, width=width) if grouped else ([f() for f in fns], None)
@@ -206,6 +216,13 @@ class _Base(nn.Module):
             rows = sum(b[0].shape[0] for b in batches)
             return outs, sum(r[1] * b[0].shape[0] for r, b in zip(res, batches)) / rows
         return outs
+
+    @staticmethod
+    def _slice_keys(kwargs, sl):
+        """the sampler keywords of the batch slice `sl`: per-row keys (row_seeds) go with their rows"""
+        if kwargs.get("row_seeds") is None:
+            return kwargs
+        return {**kwargs, "row_seeds": kwargs["row_seeds"][sl]}
 
     def _sampler_minibatched(self, make, y, minibatch):
         M = y.shape[0]
@@ -252,7 +269,7 @@ class ScoreModel(_Base):
         if minibatch is None:
             return sampling.get_pc_sampler(predictor_name, corrector_name, sde=sde, score_fn=self, y=y, **kwargs)
         return self._sampler_minibatched(
-            lambda sl: sampling.get_pc_sampler(predictor_name, corrector_name, sde=sde, score_fn=self, y=y[sl], **kwargs),
+            lambda sl: sampling.get_pc_sampler(predictor_name, corrector_name, sde=sde, score_fn=self, y=y[sl], **self._slice_keys(kwargs, sl)),
             y, minibatch)
 
     def get_ode_sampler(self, y, N=None, minibatch=1, **kwargs):
@@ -262,19 +279,24 @@ class ScoreModel(_Base):
         kwargs = {"eps": self.t_eps, **kwargs}
         if minibatch is None:
             return sampling.get_ode_sampler(sde, self, y=y, **kwargs)
-        return self._sampler_minibatched(lambda sl: sampling.get_ode_sampler(sde, self, y=y[sl], **kwargs), y, minibatch)
+        return self._sampler_minibatched(lambda sl: sampling.get_ode_sampler(sde, self, y=y[sl], **self._slice_keys(kwargs, sl)), y, minibatch)
 
     def enhance_batch(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", N=50,
-                      corrector_steps=1, snr=0.5, return_nfe=False, lengths=None, **kwargs):
+                      corrector_steps=1, snr=0.5, return_nfe=False, lengths=None, row_seeds=None, **kwargs):
         """B equal-length utterances y [B, L] in one sampler run.  Every op on the path is per utterance, the Langevin
         corrector runs with per-row step sizes and the ODE sampler with one Runge-Kutta step controller per row (the
         reference solves one utterance per solve_ivp call), so with INJECTED noise (noise_fn) row b equals enhance(y[b:b+1])
-        for every sampler / predictor / corrector; with the in-kernel Philox stream (seed=) rows are independent draws but
-        not the draws a batch-1 call with the same seed would make (the counter is the position in the batch).
+        for every sampler / predictor / corrector.  The in-kernel Philox noise has two forms.  seed=: ONE stream for the call,
+        the counter is the position in the batch - rows are independent draws, but a row's draws depend on where it sits.
+        row_seeds=[s_0 ... s_{B-1}] (ints in [0, 2^63), instead of seed / noise_fn): row b has its own key and draws exactly
+        what enhance(y[b:b+1], seed=s_b) draws, so row b equals that call wherever and with whatever it is batched - to fp32
+        rounding, and bit for bit in every precision under storm_amd.set_batch_invariant().
         For sampler_type="ode" the returned nfe is the number of score evaluations executed (= the slowest row's count).
         lengths: ragged micro-batch - rows of different sample counts that share one padded frame count
         (storm_amd.distributed.bucket_by_frames); y is zero filled to the longest row and so is the result."""
         Y, peak, T_orig = self._prepare(y, lengths)
+        if row_seeds is not None:
+            kwargs["row_seeds"] = row_seeds
         if sampler_type == "pc":
             kwargs.setdefault("langevin_per_row", True)
             sampler = self.get_pc_sampler(predictor, corrector, Y, N=N, corrector_steps=corrector_steps, snr=snr,
@@ -365,14 +387,17 @@ class StochasticRegenerationModel(_Base):
                                            conditioning=conditioning, **kwargs)
         return self._sampler_minibatched(
             lambda sl: sampling.get_pc_sampler(predictor_name, corrector_name, sde=sde, score_fn=self.forward_score,
-                                               y=y[sl], conditioning=[c[sl] for c in conditioning], **kwargs),
+                                               y=y[sl], conditioning=[c[sl] for c in conditioning], **self._slice_keys(kwargs, sl)),
             y, minibatch)
 
     def enhance_batch(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="none", N=30,
                       corrector_steps=1, snr=0.5, denoiser_only=False, return_nfe=False, return_stft=False, lengths=None,
-                      **kwargs):
+                      row_seeds=None, **kwargs):
+        """row_seeds: one Philox key per row, as in ScoreModel.enhance_batch (row b draws what its batch-1 run with seed = s_b draws)"""
         Y, peak, T_orig = self._prepare(y, lengths)
         kwargs.setdefault("langevin_per_row", True)
+        if row_seeds is not None:
+            kwargs["row_seeds"] = row_seeds
         nfe = 0
         with torch.no_grad():
             Y_denoised = self.forward_denoiser(Y) if self.denoiser_net is not None else None

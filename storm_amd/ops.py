@@ -351,27 +351,67 @@ def _n_per_batch(x):
     return x.numel() // x.shape[0]
 
 
-def ouve_prior(sde, y, z=None, seed=0, offset=0):
+def row_seed_table(row_seeds, device):
+    """Per-row Philox keys as the *_rs kernels read them: an int64 tensor [B] on `device`, values in [0, 2^63) (the kernels read
+    the same 64 bits as unsigned keys).  Takes a sequence of ints or an int64 tensor."""
+    if not torch.is_tensor(row_seeds):
+        vals = [int(v) for v in row_seeds]
+        if any(v < 0 or v >= 2 ** 63 for v in vals):
+            raise ValueError("row_seeds must lie in [0, 2^63)")
+        row_seeds = torch.tensor(vals, dtype=torch.int64)
+    if row_seeds.dtype != torch.int64 or row_seeds.dim() != 1:
+        raise ValueError(f"row_seeds must be an int64 tensor [B], got {row_seeds.dtype} {tuple(row_seeds.shape)}")
+    return row_seeds.to(device).contiguous()
+
+
+def _keys(row_seeds, like):
+    """the key table of a call on the batch `like` (one key per row), on its device"""
+    k = row_seed_table(row_seeds, like.device)
+    if k.shape[0] != like.shape[0]:
+        raise ValueError(f"row_seeds has {k.shape[0]} keys for a batch of {like.shape[0]} rows")
+    return k
+
+
+def ouve_prior(sde, y, z=None, seed=0, offset=0, row_seeds=None):
+    """row_seeds (here and in every op that takes seed=, offset=): int64 device tensor [B] of per-row Philox keys - row b draws
+    what the batch-1 call with seed = row_seeds[b] draws (the storm_*_rs entry points) instead of its share of the stream of `seed`"""
     x = torch.empty_like(y)
+    if row_seeds is not None:
+        k = _keys(row_seeds, y)
+        L.check(L.lib().storm_ouve_prior_rs(L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(_r(x)), y.shape[0], _n_per_batch(y), _ouve(sde),
+                                            0, offset, L.ptr(k), L.stream()), "storm_ouve_prior_rs")
+        return x
     L.check(L.lib().storm_ouve_prior(L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(_r(x)), y.shape[0], _n_per_batch(y), _ouve(sde),
                                      seed, offset, L.stream()), "storm_ouve_prior")
     return x
 
 
-def ouve_ald_step(sde, x, score, t, snr, z=None, seed=0, offset=0):
+def ouve_ald_step(sde, x, score, t, snr, z=None, seed=0, offset=0, row_seeds=None):
     """In place on x; returns (x, x_mean)."""
     xm = torch.empty_like(x)
     t = _t32(t)
+    if row_seeds is not None:
+        k = _keys(row_seeds, x)
+        L.check(L.lib().storm_ouve_ald_step_rs(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(z)), L.ptr(t),
+                                               x.shape[0], _n_per_batch(x), _ouve(sde), float(snr), 0, offset, L.ptr(k), L.stream()),
+                "storm_ouve_ald_step_rs")
+        return x, xm
     L.check(L.lib().storm_ouve_ald_step(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(z)), L.ptr(t),
                                         x.shape[0], _n_per_batch(x), _ouve(sde), float(snr), seed, offset, L.stream()),
             "storm_ouve_ald_step")
     return x, xm
 
 
-def ouve_predictor_step(sde, x, score, y, t, kind=0, z=None, noise_free=False, seed=0, offset=0):
+def ouve_predictor_step(sde, x, score, y, t, kind=0, z=None, noise_free=False, seed=0, offset=0, row_seeds=None):
     """In place on x; returns (x, x_mean)."""
     xm = torch.empty_like(x)
     t = _t32(t)
+    if row_seeds is not None:
+        k = _keys(row_seeds, x)
+        L.check(L.lib().storm_ouve_predictor_step_rs(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(y)), L.ptr(_r(z)),
+                                                     L.ptr(t), x.shape[0], _n_per_batch(x), _ouve(sde), kind, int(noise_free),
+                                                     0, offset, L.ptr(k), L.stream()), "storm_ouve_predictor_step_rs")
+        return x, xm
     L.check(L.lib().storm_ouve_predictor_step(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(y)), L.ptr(_r(z)),
                                               L.ptr(t), x.shape[0], _n_per_batch(x), _ouve(sde), kind, int(noise_free),
                                               seed, offset, L.stream()), "storm_ouve_predictor_step")
@@ -446,20 +486,31 @@ def _rows32(v, like):
     return v.to(device=like.device, dtype=torch.float32).contiguous()
 
 
-def sde_prior_rows(y, std_rows, z=None, seed=0, offset=0):
+def sde_prior_rows(y, std_rows, z=None, seed=0, offset=0, row_seeds=None):
     """y + z * std_b (OUVPSDE.prior_sampling, sdes.py:306-310); z=None draws in-kernel (Philox)."""
     x = torch.empty_like(y)
     std_rows = _rows32(std_rows, y)
+    if row_seeds is not None:
+        k = _keys(row_seeds, y)
+        L.check(L.lib().storm_sde_prior_rows_rs(L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(_r(x)), L.ptr(std_rows), y.shape[0], _n_per_batch(y),
+                                                0, offset, L.ptr(k), L.stream()), "storm_sde_prior_rows_rs")
+        return x
     L.check(L.lib().storm_sde_prior_rows(L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(_r(x)), L.ptr(std_rows), y.shape[0], _n_per_batch(y),
                                          seed, offset, L.stream()), "storm_sde_prior_rows")
     return x
 
 
-def sde_predictor_step_rows(sde, x, score, y, t, kind=0, z=None, noise_free=False, seed=0, offset=0):
+def sde_predictor_step_rows(sde, x, score, y, t, kind=0, z=None, noise_free=False, seed=0, offset=0, row_seeds=None):
     """Predictor update for an SDE with drift a(t) (y - x) and diffusion g(t) given by its `drift_rows(t)` / `diffusion(t)`
     (fp32 [B], the reference's own expressions).  In place on x; returns (x, x_mean)."""
     xm = torch.empty_like(x)
     a, g = _rows32(sde.drift_rows(t), x), _rows32(sde.diffusion(t), x)
+    if row_seeds is not None:
+        k = _keys(row_seeds, x)
+        L.check(L.lib().storm_sde_predictor_step_rows_rs(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(a),
+                                                         L.ptr(g), x.shape[0], _n_per_batch(x), int(sde.N), kind, int(noise_free), 0,
+                                                         offset, L.ptr(k), L.stream()), "storm_sde_predictor_step_rows_rs")
+        return x, xm
     L.check(L.lib().storm_sde_predictor_step_rows(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(a),
                                                   L.ptr(g), x.shape[0], _n_per_batch(x), int(sde.N), kind, int(noise_free), seed,
                                                   offset, L.stream()), "storm_sde_predictor_step_rows")
@@ -567,8 +618,13 @@ def copy_rows(dst, src, mask):
     return dst
 
 
-def complex_randn(shape, device, seed, offset):
+def complex_randn(shape, device, seed, offset, row_seeds=None):
+    """standard complex normal noise of `shape`; with row_seeds (int64 device [shape[0]]) row b = complex_randn(shape[1:], row_seeds[b], offset)"""
     z = torch.empty(shape, dtype=torch.complex64, device=device)
+    if row_seeds is not None:
+        k = _keys(row_seeds, z)
+        L.check(L.lib().storm_complex_randn_rs(L.ptr(_r(z)), z.shape[0], _n_per_batch(z), 0, offset, L.ptr(k), L.stream()), "storm_complex_randn_rs")
+        return z
     L.check(L.lib().storm_complex_randn(L.ptr(_r(z)), z.numel(), seed, offset, L.stream()), "storm_complex_randn")
     return z
 

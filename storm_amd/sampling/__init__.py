@@ -2,7 +2,7 @@
 
 ``get_pc_sampler(...)`` keeps the reference signature and returns ``fn() -> (x, nfe)``.  Extra
 keyword-only knobs: ``noise_fn`` (inject the draws, for parity runs), ``seed`` (in-kernel Philox
-stream for production runs), ``langevin_per_row`` / ``langevin_group`` (how the Langevin corrector's batch-coupled
+stream for production runs), ``row_seeds`` (one Philox key per row: row b draws what its batch-1 run with seed = row_seeds[b] draws), ``langevin_per_row`` / ``langevin_group`` (how the Langevin corrector's batch-coupled
 step size is formed, see LangevinCorrector).  All update functions work IN PLACE on the state they are handed."""
 import torch
 
@@ -16,12 +16,12 @@ __all__ = ["PredictorRegistry", "CorrectorRegistry", "Predictor", "Corrector", "
 
 def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=True, eps=3e-2, snr=0.1,
                    corrector_steps=1, probability_flow: bool = False, conditioning=None, intermediate=False,
-                   noise_fn=None, seed=None, langevin_per_row=False, langevin_group=None, **kwargs):
+                   noise_fn=None, seed=None, langevin_per_row=False, langevin_group=None, row_seeds=None, **kwargs):
     """PC sampler (sampling/__init__.py:27-68): prior draw, then N x (corrector, predictor) on the
     time grid linspace(T, eps, N); returns the last predictor mean and nfe = N (corrector_steps + 1)."""
     predictor_cls = PredictorRegistry.get_by_name(predictor_name)
     corrector_cls = CorrectorRegistry.get_by_name(corrector_name)
-    noise = NoiseSource(seed=seed, noise_fn=noise_fn)
+    noise = NoiseSource(seed=seed, noise_fn=noise_fn, row_seeds=row_seeds)
     if predictor_name == "none":
         predictor = predictor_cls()
     else:
@@ -35,8 +35,8 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=Tru
     def pc_sampler():
         with torch.no_grad():
             yy = y.contiguous()
-            z, sd, off = noise.next(yy)
-            xt = sde.prior_sampling(yy.shape, yy, z=z, seed=sd, offset=off)
+            z, keys = noise.draw(yy)
+            xt = sde.prior_sampling(yy.shape, yy, z=z, **keys)
             xt_mean = xt
             timesteps = torch.linspace(sde.T, eps, sde.N, device=yy.device)
             vec_ts = (torch.ones(sde.N, yy.shape[0], device=yy.device) * timesteps[:, None]).contiguous()

@@ -42,9 +42,9 @@ class LangevinCorrector(Corrector):
         x_mean = x
         for _ in range(self.n_steps):
             grad = _score(self.score_fn, x, t, args, kwargs)
-            z, seed, off = self.noise.next(x)
+            z, keys = self.noise.draw(x)
             if z is None:
-                z = ops.complex_randn(x.shape, x.device, seed, off)
+                z = ops.complex_randn(x.shape, x.device, **keys)
             x, x_mean = ops.langevin_step(x.contiguous(), grad.contiguous(), z.contiguous(), self.snr, per_row=self.per_row,
                                           group=self.group)
         return x, x_mean
@@ -63,9 +63,8 @@ class AnnealedLangevinDynamics(Corrector):
         x_mean = x
         for _ in range(self.n_steps):
             grad = _score(self.score_fn, x, t, args, kwargs)
-            z, seed, off = self.noise.next(x)
-            x, x_mean = ops.ouve_ald_step(self.sde, x.contiguous(), grad.contiguous(), t.contiguous(), self.snr, z=z,
-                                          seed=seed, offset=off)
+            z, keys = self.noise.draw(x)
+            x, x_mean = ops.ouve_ald_step(self.sde, x.contiguous(), grad.contiguous(), t.contiguous(), self.snr, z=z, **keys)
         return x, x_mean
 
 

@@ -38,7 +38,8 @@ _ERR_EXP = -1.0 / 5.0
 
 
 def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e-5, atol=1e-5, method="RK45",
-                    eps=3e-2, device=None, noise_fn=None, seed=None, conditioning=None, per_row=False, compact=True, **kwargs):
+                    eps=3e-2, device=None, noise_fn=None, seed=None, conditioning=None, per_row=False, compact=True, row_seeds=None,
+                    **kwargs):
     """Probability-flow ODE sampler: Dormand-Prince RK45 with scipy's step controller (solve_ivp's `RK45`, which
     sampling/__init__.py:71-141 runs on the host over the flattened COMPLEX state: its norms are
     ||v|| / sqrt(n) over the n complex elements).  Everything per element runs in HIP kernels: one fused pass per
@@ -46,13 +47,15 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
     sums once per attempted step (they decide acceptance) - no per-stage synchronisation.
     per_row: one step controller per row instead of one for the whole batch (module docstring).
     compact (per_row only): rows that reached eps leave the batch instead of idling in every further evaluation.
+    row_seeds: one Philox key per row for the prior draw (row b starts from what its batch-1 run with seed = row_seeds[b] starts
+    from); the draw is made on the whole batch, before any row leaves it.
     Returns fn() -> (x, nfe); nfe = score evaluations executed; fn.nfev_rows = evaluations each row needed on its own;
     fn.rows_evaluated = rows summed over the executed evaluations (what the network really computed)."""
     if method != "RK45":
         raise NotImplementedError("only RK45 (Dormand-Prince) is implemented on the device")
     from .. import ops
     from .noise import NoiseSource
-    noise = NoiseSource(seed=seed, noise_fn=noise_fn)
+    noise = NoiseSource(seed=seed, noise_fn=noise_fn, row_seeds=row_seeds)
     predictor = ReverseDiffusionPredictor(sde, score_fn, probability_flow=False, noise=noise)
     rsde = sde.reverse(score_fn, probability_flow=True)
 
@@ -89,9 +92,9 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
                 s = sumsq_rows.cpu().tolist()
                 return [math.sqrt(sum(s[b] for b in ids) / (n_row * len(ids))) for ids in groups]
 
-            zz, sd, off = noise.next(yy)
+            zz, keys = noise.draw(yy)
             # (a caller's start state is cloned: accepted rows are copied into x32 in place, and the caller may reuse z)
-            x32 = sde.prior_sampling(yy.shape, yy, z=zz, seed=sd, offset=off).contiguous() if z is None else z.contiguous().clone()
+            x32 = sde.prior_sampling(yy.shape, yy, z=zz, **keys).contiguous() if z is None else z.contiguous().clone()
             x = x32.to(torch.complex128)                      # the solver state is complex128, as in scipy (module docstring)
             t_end, direction = float(eps), -1.0
             t = [float(sde.T)] * G

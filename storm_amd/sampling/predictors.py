@@ -35,12 +35,12 @@ class Predictor(abc.ABC):
     def _step(self, kind, x, t, args, kwargs, noise_free=False):
         y = args[0]
         score = _score(self.score_fn, x, t, args, kwargs)
-        z, seed, off = (None, 0, 0) if noise_free else self.noise.next(x)
+        z, keys = (None, {}) if noise_free else self.noise.draw(x)
         if not isinstance(self.sde, OUVESDE):      # coefficient-table form: a(t_b), g(t_b) from the SDE's own fp32 expressions
             return ops.sde_predictor_step_rows(self.sde, x.contiguous(), score.contiguous(), y.contiguous(), t.contiguous(),
-                                               kind=kind, z=z, noise_free=noise_free, seed=seed, offset=off)
+                                               kind=kind, z=z, noise_free=noise_free, **keys)
         return ops.ouve_predictor_step(self.sde, x.contiguous(), score.contiguous(), y.contiguous(), t.contiguous(),
-                                       kind=kind, z=z, noise_free=noise_free, seed=seed, offset=off)
+                                       kind=kind, z=z, noise_free=noise_free, **keys)
 
 
 @PredictorRegistry.register("euler_maruyama")

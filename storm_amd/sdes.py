@@ -140,11 +140,11 @@ class OUVESDE(SDE):
     def marginal_prob(self, x0, t, y):
         return self._mean(x0, t, y), self._std(t)
 
-    def prior_sampling(self, shape, y, z=None, seed=0, offset=0):
+    def prior_sampling(self, shape, y, z=None, seed=0, offset=0, row_seeds=None):
         """y + z * std(1)  (sdes.py:233-237) — fused HIP kernel; z=None draws in-kernel (Philox)."""
         if tuple(shape) != tuple(y.shape):
             warnings.warn(f"Target shape {shape} does not match shape of y {y.shape}! Ignoring target shape.")
-        return ops.ouve_prior(self, y.contiguous(), z=z, seed=seed, offset=offset)
+        return ops.ouve_prior(self, y.contiguous(), z=z, seed=seed, offset=offset, row_seeds=row_seeds)
 
     def prior_logp(self, z):
         raise NotImplementedError("prior_logp for OU SDE not yet implemented!")
@@ -204,12 +204,12 @@ class OUVPSDE(SDE):
     def marginal_prob(self, x0, t, y):
         return self._mean(x0, t, y), self._std(t)
 
-    def prior_sampling(self, shape, y, z=None, seed=0, offset=0):
+    def prior_sampling(self, shape, y, z=None, seed=0, offset=0, row_seeds=None):
         """y + z * std(1)  (sdes.py:306-310) — fused HIP kernel; z=None draws in-kernel (Philox)."""
         if tuple(shape) != tuple(y.shape):
             warnings.warn(f"Target shape {shape} does not match shape of y {y.shape}! Ignoring target shape.")
         std = self._std(torch.ones((y.shape[0],), device=y.device))
-        return ops.sde_prior_rows(y.contiguous(), std, z=z, seed=seed, offset=offset)
+        return ops.sde_prior_rows(y.contiguous(), std, z=z, seed=seed, offset=offset, row_seeds=row_seeds)
 
     def prior_logp(self, z):
         raise NotImplementedError("prior_logp for OU SDE not yet implemented!")
