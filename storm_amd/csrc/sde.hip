@@ -1,8 +1,9 @@
-// OUVE SDE steps of the predictor-corrector sampler on the complex64 state.
-// Reference map in include/storm_hip.h.  One fused elementwise kernel per update rule; the
-// per-batch coefficients (std(t), g(t), step sizes) are computed in-kernel from t[b] in fp64
-// and rounded once, the state update follows the reference's fp32 op order.  Noise is either
-// injected (parity runs) or generated in-kernel with Philox4x32-10 + Box-Muller.
+// SDE steps of the predictor-corrector sampler on the complex64 state.
+// Reference map in include/storm_hip.h.  One fused elementwise kernel per update rule, templated on where row b's
+// coefficients come from (Coef: computed in-kernel from t[b] in fp64 and rounded once for OUVE, or read from the caller's
+// fp32 tables for any other linear-drift SDE) and on where a generated draw takes its Philox key from (Key: one seed for the
+// call, or a key per row); the state update follows the reference's fp32 op order.  Noise is either injected (parity runs)
+// or generated in-kernel with Philox4x32-10 + Box-Muller.
 #include "common.h"
 
 namespace storm {
@@ -62,16 +63,44 @@ __device__ inline float ouve_g(const Ouve& o, double t) {
     return (float)(o.smin * pow(o.smax / o.smin, t) * sqrt(2.0 * o.logsig));
 }
 
-template <class Key>
-__global__ void ouve_prior_kernel(const float* __restrict__ y, const float* __restrict__ z, float* __restrict__ x,
-                                  long long n, storm_ouve p, Key key, uint64_t offset) {
+// Where an update takes row b's coefficients from: a (the drift is a (y - x)), the diffusion g, the perturbation std.  By-value
+// kernel arguments like the keys; a kernel evaluates what it needs once per thread, ahead of the element loop.
+struct OuveCoef {                                  // derived in-kernel from t[b] (device [B])
+    storm_ouve p; const float* t;
+    __device__ float a(int) const { return p.theta; }
+    __device__ float g(int b) const { return ouve_g(make_ouve(p), (double)t[b]); }
+};
+struct OuvePriorCoef {                             // the prior is drawn at t = T = 1 whatever the batch
+    storm_ouve p;
+    __device__ float std(int) const { return ouve_std(make_ouve(p), 1.0); }
+};
+// coefficient tables (device fp32 [B]; a call hands the ones its kernel reads): any SDE  dx = a(t) (y - x) dt + g(t) dw  (OUVPSDE,
+// sdes.py:255-326: a = 1/2 stiffness beta(t), g = sqrt(beta(t))).  The caller evaluates a(t_b), g(t_b), std(t_b) in the reference's
+// own fp32 torch expressions; the state update is the same op order for every source (SDE.discretize sdes.py:86-90,
+// RSDE.discretize :147-157, rsde_parts :123-145, predictors.py:46-69).
+struct TableCoef {
+    const float* a_rows; const float* g_rows; const float* std_rows;
+    __device__ float a(int b) const { return a_rows[b]; }
+    __device__ float g(int b) const { return g_rows[b]; }
+    __device__ float std(int b) const { return std_rows[b]; }
+};
+struct ThetaTableCoef {                            // OUVE's constant drift factor beside a g table (storm_ouve_pf_drift_g)
+    float theta; const float* g_rows;
+    __device__ float a(int) const { return theta; }
+    __device__ float g(int b) const { return g_rows[b]; }
+};
+
+// x = y + z * std_b  (OUVESDE.prior_sampling sdes.py:233-237, OUVPSDE.prior_sampling :306-310)
+template <class Coef, class Key>
+__global__ void prior_kernel(const float* __restrict__ y, const float* __restrict__ z, float* __restrict__ x, long long n,
+                             Coef coef, Key key, uint64_t offset) {
     const int b = blockIdx.y;
-    const float std1 = ouve_std(make_ouve(p), 1.0);
+    const float sd = coef.std(b);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const long long k = (long long)b * n + i;
         const float2 yy = reinterpret_cast<const float2*>(y)[k];
         const float2 zz = get_noise(z, b, i, k, key, offset);
-        reinterpret_cast<float2*>(x)[k] = make_float2(yy.x + zz.x * std1, yy.y + zz.y * std1);
+        reinterpret_cast<float2*>(x)[k] = make_float2(yy.x + zz.x * sd, yy.y + zz.y * sd);
     }
 }
 
@@ -95,18 +124,14 @@ __global__ void ouve_ald_kernel(float* __restrict__ x, float* __restrict__ x_mea
     }
 }
 
-template <class Key>
-__global__ void ouve_predictor_kernel(float* __restrict__ x, float* __restrict__ x_mean, const float* __restrict__ score,
-                                      const float* __restrict__ y, const float* __restrict__ z,
-                                      const float* __restrict__ t, long long n, storm_ouve p, int kind,
-                                      int noise_free, Key key, uint64_t offset) {
+template <class Coef, class Key>
+__global__ void predictor_kernel(float* __restrict__ x, float* __restrict__ x_mean, const float* __restrict__ score,
+                                 const float* __restrict__ y, const float* __restrict__ z, long long n, int N, int kind,
+                                 int noise_free, Coef coef, Key key, uint64_t offset) {
     const int b = blockIdx.y;
-    const Ouve o = make_ouve(p);
-    const float g = ouve_g(o, (double)t[b]);
-    const float theta = p.theta;
-    const float dt = (float)(1.0 / o.N);
-    const float sqdt = sqrtf(dt);
-    const float G = g * sqdt;                 // sdes.py:89 (also g * sqrt(-dt) for euler_maruyama)
+    const float a = coef.a(b), g = coef.g(b);
+    const float dt = (float)(1.0 / N);
+    const float G = g * sqrtf(dt);            // sdes.py:89 (also g * sqrt(-dt) for euler_maruyama)
     const float G2 = kind == 0 ? G * G : g * g;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const long long k = (long long)b * n + i;
@@ -115,13 +140,13 @@ __global__ void ouve_predictor_kernel(float* __restrict__ x, float* __restrict__
         const float2 s = reinterpret_cast<const float2*>(score)[k];
         float2 xm;
         if (kind == 0) {
-            // reverse diffusion: f = theta (y - x) dt; rev_f = f - G^2 s; x_mean = x - rev_f   (sdes.py:86-90,147-157)
-            const float fx = (theta * (yy.x - xx.x)) * dt, fy = (theta * (yy.y - xx.y)) * dt;
+            // reverse diffusion: f = a (y - x) dt; rev_f = f - G^2 s; x_mean = x - rev_f   (sdes.py:86-90,147-157)
+            const float fx = (a * (yy.x - xx.x)) * dt, fy = (a * (yy.y - xx.y)) * dt;
             const float rx = fx - G2 * s.x, ry = fy - G2 * s.y;
             xm = make_float2(xx.x - rx, xx.y - ry);
         } else {
-            // Euler-Maruyama: x_mean = x + (theta (y - x) - g^2 s) * (-1/N)                    (predictors.py:46-54)
-            const float dx = theta * (yy.x - xx.x) + (-G2) * s.x, dy = theta * (yy.y - xx.y) + (-G2) * s.y;
+            // Euler-Maruyama: x_mean = x + (a (y - x) - g^2 s) * (-1/N)                    (predictors.py:46-54)
+            const float dx = a * (yy.x - xx.x) + (-G2) * s.x, dy = a * (yy.y - xx.y) + (-G2) * s.y;
             xm = make_float2(xx.x + dx * (-dt), xx.y + dy * (-dt));
         }
         if (x_mean) reinterpret_cast<float2*>(x_mean)[k] = xm;
@@ -203,14 +228,15 @@ __global__ void ouve_pf_drift_kernel(float* __restrict__ out, const float* __res
     }
 }
 
-// the same with the diffusion coefficient g(t_b) handed in per row (fp32 [B]): the ODE sampler evaluates sigma_min (sigma_max /
-// sigma_min)^t sqrt(2 logsig) with the reference's own fp32 torch ops on the host (sdes.py:203-207), so the right-hand side
+// the same with the coefficients handed in per row (fp32 [B]): the ODE sampler evaluates g - for OUVE sigma_min (sigma_max /
+// sigma_min)^t sqrt(2 logsig) - with the reference's own fp32 torch ops on the host (sdes.py:203-207), so the right-hand side
 // is the reference's to the last bit - at rtol = atol = 1e-5 the first steps' error estimates sit at the fp32 noise floor and
-// an ulp in g changes which steps RK45 accepts
-__global__ void ouve_pf_drift_g_kernel(float* __restrict__ out, const float* __restrict__ x, const float* __restrict__ y,
-                                       const float* __restrict__ score, const float* __restrict__ g_rows, long long n, float theta) {
+// an ulp in g changes which steps RK45 accepts.  (The t form above rounds differently: theta d - (1/2 g^2) s.)
+template <class Coef>
+__global__ void pf_drift_kernel(float* __restrict__ out, const float* __restrict__ x, const float* __restrict__ y,
+                                const float* __restrict__ score, long long n, Coef coef) {
     const int b = blockIdx.y;
-    const float g = g_rows[b];
+    const float a = coef.a(b), g = coef.g(b);
     const float g2 = g * g;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const long long k = (long long)b * n + i;
@@ -218,72 +244,6 @@ __global__ void ouve_pf_drift_g_kernel(float* __restrict__ out, const float* __r
         const float2 yy = reinterpret_cast<const float2*>(y)[k];
         const float2 s = reinterpret_cast<const float2*>(score)[k];
         // sde_drift + (-(g^2) * score * 0.5)  in the reference's operation order (sdes.py:129-134)
-        reinterpret_cast<float2*>(out)[k] = make_float2(theta * (yy.x - xx.x) + (-g2 * s.x) * 0.5f, theta * (yy.y - xx.y) + (-g2 * s.y) * 0.5f);
-    }
-}
-
-// ---- coefficient-table forms: any SDE  dx = a(t) (y - x) dt + g(t) dw  (OUVPSDE, sdes.py:255-326: a = 1/2 stiffness beta(t),
-// g = sqrt(beta(t))).  The caller hands a(t_b), g(t_b), std(t_b) per row (device fp32 [B]) in the reference's own fp32 torch
-// expressions; the state update is the OUVE kernels' (same op order: SDE.discretize sdes.py:86-90, RSDE.discretize :147-157,
-// rsde_parts :123-145, predictors.py:46-69). -------------------------------------------------------------------------------------
-template <class Key>
-__global__ void sde_prior_rows_kernel(const float* __restrict__ y, const float* __restrict__ z, float* __restrict__ x,
-                                      const float* __restrict__ std_rows, long long n, Key key, uint64_t offset) {
-    const int b = blockIdx.y;
-    const float sd = std_rows[b];
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const long long k = (long long)b * n + i;
-        const float2 yy = reinterpret_cast<const float2*>(y)[k];
-        const float2 zz = get_noise(z, b, i, k, key, offset);
-        reinterpret_cast<float2*>(x)[k] = make_float2(yy.x + zz.x * sd, yy.y + zz.y * sd);
-    }
-}
-
-template <class Key>
-__global__ void sde_predictor_rows_kernel(float* __restrict__ x, float* __restrict__ x_mean, const float* __restrict__ score,
-                                          const float* __restrict__ y, const float* __restrict__ z, const float* __restrict__ a_rows,
-                                          const float* __restrict__ g_rows, long long n, int N, int kind, int noise_free,
-                                          Key key, uint64_t offset) {
-    const int b = blockIdx.y;
-    const float a = a_rows[b], g = g_rows[b];
-    const float dt = (float)(1.0 / N);
-    const float G = g * sqrtf(dt);
-    const float G2 = kind == 0 ? G * G : g * g;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const long long k = (long long)b * n + i;
-        const float2 xx = reinterpret_cast<const float2*>(x)[k];
-        const float2 yy = reinterpret_cast<const float2*>(y)[k];
-        const float2 s = reinterpret_cast<const float2*>(score)[k];
-        float2 xm;
-        if (kind == 0) {                      // reverse diffusion: x_mean = x - (a (y - x) dt - G^2 s)
-            const float fx = (a * (yy.x - xx.x)) * dt, fy = (a * (yy.y - xx.y)) * dt;
-            xm = make_float2(xx.x - (fx - G2 * s.x), xx.y - (fy - G2 * s.y));
-        } else {                              // Euler-Maruyama: x_mean = x + (a (y - x) - g^2 s) (-1/N)
-            const float dx = a * (yy.x - xx.x) + (-G2) * s.x, dy = a * (yy.y - xx.y) + (-G2) * s.y;
-            xm = make_float2(xx.x + dx * (-dt), xx.y + dy * (-dt));
-        }
-        if (x_mean) reinterpret_cast<float2*>(x_mean)[k] = xm;
-        if (noise_free) {
-            reinterpret_cast<float2*>(x)[k] = xm;
-        } else {
-            const float2 zz = get_noise(z, b, i, k, key, offset);
-            reinterpret_cast<float2*>(x)[k] = make_float2(xm.x + G * zz.x, xm.y + G * zz.y);
-        }
-    }
-}
-
-// probability-flow drift a_b (y - x) + (-(g_b^2) score) 1/2 in the reference's operation order (sdes.py:129-134)
-__global__ void sde_pf_drift_rows_kernel(float* __restrict__ out, const float* __restrict__ x, const float* __restrict__ y,
-                                         const float* __restrict__ score, const float* __restrict__ a_rows,
-                                         const float* __restrict__ g_rows, long long n) {
-    const int b = blockIdx.y;
-    const float a = a_rows[b], g = g_rows[b];
-    const float g2 = g * g;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const long long k = (long long)b * n + i;
-        const float2 xx = reinterpret_cast<const float2*>(x)[k];
-        const float2 yy = reinterpret_cast<const float2*>(y)[k];
-        const float2 s = reinterpret_cast<const float2*>(score)[k];
         reinterpret_cast<float2*>(out)[k] = make_float2(a * (yy.x - xx.x) + (-g2 * s.x) * 0.5f, a * (yy.y - xx.y) + (-g2 * s.y) * 0.5f);
     }
 }
@@ -442,69 +402,61 @@ static inline int ew_blocks(long long n) { long long b = (n + 255) / 256; return
 
 using namespace storm;
 
-// Every entry point that can generate noise exists twice - one seed for the call (BatchKey) or a key per row (RowKeys, the *_rs
-// names; their `seed` argument is not read) - around ONE launch function templated on the key.
-template <class Key>
-static int launch_ouve_prior(const char* who, const float* y, const float* z, float* x, int B, long long n, storm_ouve p, Key key,
-                             uint64_t offset, storm_stream_t s) {
-    STORM_CHECK(y && x && B > 0 && n > 0, "%s: bad arguments", who);
-    hipLaunchKernelGGL(ouve_prior_kernel<Key>, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, y, z, x, n, p, key, offset);
+// One launch for the "B rows x n elements" kernels: grid.y is the row, grid.x strides over the row's elements.
+template <class... P, class... A>
+static int launch_rows(void (*kernel)(P...), int B, long long n, storm_stream_t s, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, args...);
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }
+
+// Every entry point that can generate noise exists twice - one seed for the call (BatchKey) or a key per row (RowKeys, the *_rs
+// names; their `seed` argument is not read): its checks, then the update's ONE kernel with the coefficient source and the key chosen.
 extern "C" int storm_ouve_prior(const float* y, const float* z, float* x, int B, long long n, storm_ouve p,
                                 uint64_t seed, uint64_t offset, storm_stream_t s) {
-    return launch_ouve_prior("storm_ouve_prior", y, z, x, B, n, p, BatchKey{seed}, offset, s);
+    STORM_CHECK(y && x && B > 0 && n > 0, "storm_ouve_prior: bad arguments");
+    return launch_rows(prior_kernel<OuvePriorCoef, BatchKey>, B, n, s, y, z, x, n, OuvePriorCoef{p}, BatchKey{seed}, offset);
 }
 extern "C" int storm_ouve_prior_rs(const float* y, const float* z, float* x, int B, long long n, storm_ouve p,
                                    uint64_t seed, uint64_t offset, const uint64_t* row_seeds, storm_stream_t s) {
     (void)seed;
     STORM_CHECK(row_seeds, "storm_ouve_prior_rs: null row_seeds");
-    return launch_ouve_prior("storm_ouve_prior_rs", y, z, x, B, n, p, RowKeys{row_seeds}, offset, s);
+    STORM_CHECK(y && x && B > 0 && n > 0, "storm_ouve_prior_rs: bad arguments");
+    return launch_rows(prior_kernel<OuvePriorCoef, RowKeys>, B, n, s, y, z, x, n, OuvePriorCoef{p}, RowKeys{row_seeds}, offset);
 }
 
-template <class Key>
-static int launch_ouve_ald(const char* who, float* x, float* x_mean, const float* score, const float* z, const float* t, int B,
-                           long long n, storm_ouve p, float snr, Key key, uint64_t offset, storm_stream_t s) {
-    STORM_CHECK(x && score && t && B > 0 && n > 0, "%s: bad arguments", who);
-    hipLaunchKernelGGL(ouve_ald_kernel<Key>, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, x, x_mean, score, z, t, n, p, snr, key, offset);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
-}
 extern "C" int storm_ouve_ald_step(float* x, float* x_mean, const float* score, const float* z, const float* t, int B,
                                    long long n, storm_ouve p, float snr, uint64_t seed, uint64_t offset,
                                    storm_stream_t s) {
-    return launch_ouve_ald("storm_ouve_ald_step", x, x_mean, score, z, t, B, n, p, snr, BatchKey{seed}, offset, s);
+    STORM_CHECK(x && score && t && B > 0 && n > 0, "storm_ouve_ald_step: bad arguments");
+    return launch_rows(ouve_ald_kernel<BatchKey>, B, n, s, x, x_mean, score, z, t, n, p, snr, BatchKey{seed}, offset);
 }
 extern "C" int storm_ouve_ald_step_rs(float* x, float* x_mean, const float* score, const float* z, const float* t, int B,
                                       long long n, storm_ouve p, float snr, uint64_t seed, uint64_t offset,
                                       const uint64_t* row_seeds, storm_stream_t s) {
     (void)seed;
     STORM_CHECK(row_seeds, "storm_ouve_ald_step_rs: null row_seeds");
-    return launch_ouve_ald("storm_ouve_ald_step_rs", x, x_mean, score, z, t, B, n, p, snr, RowKeys{row_seeds}, offset, s);
+    STORM_CHECK(x && score && t && B > 0 && n > 0, "storm_ouve_ald_step_rs: bad arguments");
+    return launch_rows(ouve_ald_kernel<RowKeys>, B, n, s, x, x_mean, score, z, t, n, p, snr, RowKeys{row_seeds}, offset);
 }
 
-template <class Key>
-static int launch_ouve_predictor(const char* who, float* x, float* x_mean, const float* score, const float* y, const float* z,
-                                 const float* t, int B, long long n, storm_ouve p, int kind, int noise_free, Key key, uint64_t offset,
-                                 storm_stream_t s) {
-    STORM_CHECK(x && score && y && t && B > 0 && n > 0 && p.N > 0, "%s: bad arguments", who);
-    STORM_CHECK(kind == 0 || kind == 1, "%s: kind=%d", who, kind);
-    hipLaunchKernelGGL(ouve_predictor_kernel<Key>, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, x, x_mean, score, y, z, t, n, p, kind, noise_free, key, offset);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
-}
 extern "C" int storm_ouve_predictor_step(float* x, float* x_mean, const float* score, const float* y, const float* z,
                                          const float* t, int B, long long n, storm_ouve p, int kind, int noise_free,
                                          uint64_t seed, uint64_t offset, storm_stream_t s) {
-    return launch_ouve_predictor("storm_ouve_predictor_step", x, x_mean, score, y, z, t, B, n, p, kind, noise_free, BatchKey{seed}, offset, s);
+    STORM_CHECK(x && score && y && t && B > 0 && n > 0 && p.N > 0, "storm_ouve_predictor_step: bad arguments");
+    STORM_CHECK(kind == 0 || kind == 1, "storm_ouve_predictor_step: kind=%d", kind);
+    return launch_rows(predictor_kernel<OuveCoef, BatchKey>, B, n, s, x, x_mean, score, y, z, n, p.N, kind, noise_free, OuveCoef{p, t},
+                       BatchKey{seed}, offset);
 }
 extern "C" int storm_ouve_predictor_step_rs(float* x, float* x_mean, const float* score, const float* y, const float* z,
                                             const float* t, int B, long long n, storm_ouve p, int kind, int noise_free,
                                             uint64_t seed, uint64_t offset, const uint64_t* row_seeds, storm_stream_t s) {
     (void)seed;
     STORM_CHECK(row_seeds, "storm_ouve_predictor_step_rs: null row_seeds");
-    return launch_ouve_predictor("storm_ouve_predictor_step_rs", x, x_mean, score, y, z, t, B, n, p, kind, noise_free, RowKeys{row_seeds}, offset, s);
+    STORM_CHECK(x && score && y && t && B > 0 && n > 0 && p.N > 0, "storm_ouve_predictor_step_rs: bad arguments");
+    STORM_CHECK(kind == 0 || kind == 1, "storm_ouve_predictor_step_rs: kind=%d", kind);
+    return launch_rows(predictor_kernel<OuveCoef, RowKeys>, B, n, s, x, x_mean, score, y, z, n, p.N, kind, noise_free, OuveCoef{p, t},
+                       RowKeys{row_seeds}, offset);
 }
 
 extern "C" int storm_batch_l2norm(const float* v, float* out, int B, long long n, storm_stream_t s) {
@@ -518,24 +470,18 @@ extern "C" int storm_langevin_step(float* x, float* x_mean, const float* score, 
                                    const float* z_norms, int B, long long n, float snr, int mode, storm_stream_t s) {
     STORM_CHECK(x && score && z && score_norms && z_norms && B > 0 && n > 0, "storm_langevin_step: bad arguments");
     STORM_CHECK(mode >= 0 && mode <= 2, "storm_langevin_step: mode=%d", mode);
-    hipLaunchKernelGGL(langevin_kernel, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, x, x_mean, score, z, score_norms, z_norms, B, n, snr, mode);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
+    return launch_rows(langevin_kernel, B, n, s, x, x_mean, score, z, score_norms, z_norms, B, n, snr, mode);
 }
 
 extern "C" int storm_complex_randn(float* z, long long n_complex, uint64_t seed, uint64_t offset, storm_stream_t s) {
     STORM_CHECK(z && n_complex > 0, "storm_complex_randn: bad arguments");
-    hipLaunchKernelGGL(complex_randn_kernel<BatchKey>, dim3(ew_blocks(n_complex)), dim3(256), 0, (hipStream_t)s, z, n_complex, BatchKey{seed}, offset);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
+    return launch_rows(complex_randn_kernel<BatchKey>, 1, n_complex, s, z, n_complex, BatchKey{seed}, offset);
 }
 extern "C" int storm_complex_randn_rs(float* z, int B, long long n_per_row, uint64_t seed, uint64_t offset,
                                       const uint64_t* row_seeds, storm_stream_t s) {
     (void)seed;
     STORM_CHECK(z && B > 0 && n_per_row > 0 && row_seeds, "storm_complex_randn_rs: bad arguments");
-    hipLaunchKernelGGL(complex_randn_kernel<RowKeys>, dim3(ew_blocks(n_per_row), B), dim3(256), 0, (hipStream_t)s, z, n_per_row, RowKeys{row_seeds}, offset);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
+    return launch_rows(complex_randn_kernel<RowKeys>, B, n_per_row, s, z, n_per_row, RowKeys{row_seeds}, offset);
 }
 
 static int fill_terms(RkTerms& t, const float* const* K, const float* coef, int n_terms) {
@@ -594,9 +540,7 @@ extern "C" int storm_rk_combine_rows(double* out64, float* out32, const double* 
     RkTermsD t; RkRows r;
     if (int rc = fill_terms_d(t, K, coef, n_terms)) return rc;
     if (int rc = fill_rows(r, h_rows, B)) return rc;
-    hipLaunchKernelGGL(rk_combine_rows_kernel, dim3(ew_blocks(n_complex_row), B), dim3(256), 0, (hipStream_t)s, out64, out32, x, t, r, n_complex_row);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
+    return launch_rows(rk_combine_rows_kernel, B, n_complex_row, s, out64, out32, x, t, r, n_complex_row);
 }
 
 extern "C" int storm_rk_scaled_sumsq_rows(double* out, double* scratch, long long scratch_len, const double* xa, const double* xb,
@@ -631,54 +575,35 @@ extern "C" int storm_copy_rows(void* dst, const void* src, const int* row_mask, 
 extern "C" int storm_ouve_pf_drift(float* out, const float* x, const float* y, const float* score, const float* t, int B,
                                    long long n, storm_ouve p, storm_stream_t s) {
     STORM_CHECK(out && x && y && score && t && B > 0 && n > 0, "storm_ouve_pf_drift: bad arguments");
-    hipLaunchKernelGGL(ouve_pf_drift_kernel, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, out, x, y, score, t, n, p);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
+    return launch_rows(ouve_pf_drift_kernel, B, n, s, out, x, y, score, t, n, p);
 }
 
 extern "C" int storm_ouve_pf_drift_g(float* out, const float* x, const float* y, const float* score, const float* g_rows, int B,
                                      long long n, float theta, storm_stream_t s) {
     STORM_CHECK(out && x && y && score && g_rows && B > 0 && n > 0, "storm_ouve_pf_drift_g: bad arguments");
-    hipLaunchKernelGGL(ouve_pf_drift_g_kernel, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, out, x, y, score, g_rows, n, theta);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
+    return launch_rows(pf_drift_kernel<ThetaTableCoef>, B, n, s, out, x, y, score, n, ThetaTableCoef{theta, g_rows});
 }
 
-template <class Key>
-static int launch_sde_prior_rows(const char* who, const float* y, const float* z, float* x, const float* std_rows, int B, long long n,
-                                 Key key, uint64_t offset, storm_stream_t s) {
-    STORM_CHECK(y && x && std_rows && B > 0 && n > 0, "%s: bad arguments", who);
-    hipLaunchKernelGGL(sde_prior_rows_kernel<Key>, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, y, z, x, std_rows, n, key, offset);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
-}
 extern "C" int storm_sde_prior_rows(const float* y, const float* z, float* x, const float* std_rows, int B, long long n,
                                     uint64_t seed, uint64_t offset, storm_stream_t s) {
-    return launch_sde_prior_rows("storm_sde_prior_rows", y, z, x, std_rows, B, n, BatchKey{seed}, offset, s);
+    STORM_CHECK(y && x && std_rows && B > 0 && n > 0, "storm_sde_prior_rows: bad arguments");
+    return launch_rows(prior_kernel<TableCoef, BatchKey>, B, n, s, y, z, x, n, TableCoef{nullptr, nullptr, std_rows}, BatchKey{seed}, offset);
 }
 extern "C" int storm_sde_prior_rows_rs(const float* y, const float* z, float* x, const float* std_rows, int B, long long n,
                                        uint64_t seed, uint64_t offset, const uint64_t* row_seeds, storm_stream_t s) {
     (void)seed;
     STORM_CHECK(row_seeds, "storm_sde_prior_rows_rs: null row_seeds");
-    return launch_sde_prior_rows("storm_sde_prior_rows_rs", y, z, x, std_rows, B, n, RowKeys{row_seeds}, offset, s);
+    STORM_CHECK(y && x && std_rows && B > 0 && n > 0, "storm_sde_prior_rows_rs: bad arguments");
+    return launch_rows(prior_kernel<TableCoef, RowKeys>, B, n, s, y, z, x, n, TableCoef{nullptr, nullptr, std_rows}, RowKeys{row_seeds}, offset);
 }
 
-template <class Key>
-static int launch_sde_predictor_rows(const char* who, float* x, float* x_mean, const float* score, const float* y, const float* z,
-                                     const float* a_rows, const float* g_rows, int B, long long n, int N, int kind, int noise_free,
-                                     Key key, uint64_t offset, storm_stream_t s) {
-    STORM_CHECK(x && score && y && a_rows && g_rows && B > 0 && n > 0 && N > 0, "%s: bad arguments", who);
-    STORM_CHECK(kind == 0 || kind == 1, "%s: kind=%d", who, kind);
-    hipLaunchKernelGGL(sde_predictor_rows_kernel<Key>, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, x, x_mean, score, y, z, a_rows, g_rows, n, N, kind,
-                       noise_free, key, offset);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
-}
 extern "C" int storm_sde_predictor_step_rows(float* x, float* x_mean, const float* score, const float* y, const float* z,
                                              const float* a_rows, const float* g_rows, int B, long long n, int N, int kind,
                                              int noise_free, uint64_t seed, uint64_t offset, storm_stream_t s) {
-    return launch_sde_predictor_rows("storm_sde_predictor_step_rows", x, x_mean, score, y, z, a_rows, g_rows, B, n, N, kind, noise_free,
-                                     BatchKey{seed}, offset, s);
+    STORM_CHECK(x && score && y && a_rows && g_rows && B > 0 && n > 0 && N > 0, "storm_sde_predictor_step_rows: bad arguments");
+    STORM_CHECK(kind == 0 || kind == 1, "storm_sde_predictor_step_rows: kind=%d", kind);
+    return launch_rows(predictor_kernel<TableCoef, BatchKey>, B, n, s, x, x_mean, score, y, z, n, N, kind, noise_free,
+                       TableCoef{a_rows, g_rows, nullptr}, BatchKey{seed}, offset);
 }
 extern "C" int storm_sde_predictor_step_rows_rs(float* x, float* x_mean, const float* score, const float* y, const float* z,
                                                 const float* a_rows, const float* g_rows, int B, long long n, int N, int kind,
@@ -686,16 +611,16 @@ extern "C" int storm_sde_predictor_step_rows_rs(float* x, float* x_mean, const f
                                                 storm_stream_t s) {
     (void)seed;
     STORM_CHECK(row_seeds, "storm_sde_predictor_step_rows_rs: null row_seeds");
-    return launch_sde_predictor_rows("storm_sde_predictor_step_rows_rs", x, x_mean, score, y, z, a_rows, g_rows, B, n, N, kind, noise_free,
-                                     RowKeys{row_seeds}, offset, s);
+    STORM_CHECK(x && score && y && a_rows && g_rows && B > 0 && n > 0 && N > 0, "storm_sde_predictor_step_rows_rs: bad arguments");
+    STORM_CHECK(kind == 0 || kind == 1, "storm_sde_predictor_step_rows_rs: kind=%d", kind);
+    return launch_rows(predictor_kernel<TableCoef, RowKeys>, B, n, s, x, x_mean, score, y, z, n, N, kind, noise_free,
+                       TableCoef{a_rows, g_rows, nullptr}, RowKeys{row_seeds}, offset);
 }
 
 extern "C" int storm_sde_pf_drift_rows(float* out, const float* x, const float* y, const float* score, const float* a_rows,
                                        const float* g_rows, int B, long long n, storm_stream_t s) {
     STORM_CHECK(out && x && y && score && a_rows && g_rows && B > 0 && n > 0, "storm_sde_pf_drift_rows: bad arguments");
-    hipLaunchKernelGGL(sde_pf_drift_rows_kernel, dim3(ew_blocks(n), B), dim3(256), 0, (hipStream_t)s, out, x, y, score, a_rows, g_rows, n);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
+    return launch_rows(pf_drift_kernel<TableCoef>, B, n, s, out, x, y, score, n, TableCoef{a_rows, g_rows, nullptr});
 }
 
 extern "C" int storm_si_sdr(const float* s, const float* s_hat, float* out, int B, long long n, long long stride_s,

@@ -372,17 +372,22 @@ def _keys(row_seeds, like):
     return k
 
 
+def _noise_call(name, args, seed, offset, row_seeds, like):
+    """The one call of a noise-drawing entry point: `name` with args (its arguments up to `seed`), seed, offset - or, with row_seeds,
+    its per-row-key form name + "_rs": seed 0 (not read) and the key table of the batch `like` after offset."""
+    keys = ()
+    if row_seeds is not None:
+        k = _keys(row_seeds, like)                          # (kept alive in a local: a temporary would be freed before the launch)
+        name, seed, keys = name + "_rs", 0, (L.ptr(k),)
+    L.check(getattr(L.lib(), name)(*args, seed, offset, *keys, L.stream()), name)
+
+
 def ouve_prior(sde, y, z=None, seed=0, offset=0, row_seeds=None):
     """row_seeds (here and in every op that takes seed=, offset=): int64 device tensor [B] of per-row Philox keys - row b draws
     what the batch-1 call with seed = row_seeds[b] draws (the storm_*_rs entry points) instead of its share of the stream of `seed`"""
     x = torch.empty_like(y)
-    if row_seeds is not None:
-        k = _keys(row_seeds, y)
-        L.check(L.lib().storm_ouve_prior_rs(L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(_r(x)), y.shape[0], _n_per_batch(y), _ouve(sde),
-                                            0, offset, L.ptr(k), L.stream()), "storm_ouve_prior_rs")
-        return x
-    L.check(L.lib().storm_ouve_prior(L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(_r(x)), y.shape[0], _n_per_batch(y), _ouve(sde),
-                                     seed, offset, L.stream()), "storm_ouve_prior")
+    _noise_call("storm_ouve_prior", (L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(_r(x)), y.shape[0], _n_per_batch(y), _ouve(sde)),
+                seed, offset, row_seeds, y)
     return x
 
 
@@ -390,15 +395,8 @@ def ouve_ald_step(sde, x, score, t, snr, z=None, seed=0, offset=0, row_seeds=Non
     """In place on x; returns (x, x_mean)."""
     xm = torch.empty_like(x)
     t = _t32(t)
-    if row_seeds is not None:
-        k = _keys(row_seeds, x)
-        L.check(L.lib().storm_ouve_ald_step_rs(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(z)), L.ptr(t),
-                                               x.shape[0], _n_per_batch(x), _ouve(sde), float(snr), 0, offset, L.ptr(k), L.stream()),
-                "storm_ouve_ald_step_rs")
-        return x, xm
-    L.check(L.lib().storm_ouve_ald_step(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(z)), L.ptr(t),
-                                        x.shape[0], _n_per_batch(x), _ouve(sde), float(snr), seed, offset, L.stream()),
-            "storm_ouve_ald_step")
+    _noise_call("storm_ouve_ald_step", (L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(z)), L.ptr(t), x.shape[0], _n_per_batch(x),
+                                        _ouve(sde), float(snr)), seed, offset, row_seeds, x)
     return x, xm
 
 
@@ -406,15 +404,8 @@ def ouve_predictor_step(sde, x, score, y, t, kind=0, z=None, noise_free=False, s
     """In place on x; returns (x, x_mean)."""
     xm = torch.empty_like(x)
     t = _t32(t)
-    if row_seeds is not None:
-        k = _keys(row_seeds, x)
-        L.check(L.lib().storm_ouve_predictor_step_rs(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(y)), L.ptr(_r(z)),
-                                                     L.ptr(t), x.shape[0], _n_per_batch(x), _ouve(sde), kind, int(noise_free),
-                                                     0, offset, L.ptr(k), L.stream()), "storm_ouve_predictor_step_rs")
-        return x, xm
-    L.check(L.lib().storm_ouve_predictor_step(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(y)), L.ptr(_r(z)),
-                                              L.ptr(t), x.shape[0], _n_per_batch(x), _ouve(sde), kind, int(noise_free),
-                                              seed, offset, L.stream()), "storm_ouve_predictor_step")
+    _noise_call("storm_ouve_predictor_step", (L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(t), x.shape[0],
+                                              _n_per_batch(x), _ouve(sde), kind, int(noise_free)), seed, offset, row_seeds, x)
     return x, xm
 
 
@@ -463,15 +454,6 @@ def si_sdr(s, s_hat, eps=0.0):
     return out
 
 
-def ouve_pf_drift(sde, x, y, score, t):
-    """theta (y - x) - 1/2 g(t)^2 score: the right-hand side of the probability-flow ODE in one pass."""
-    out = torch.empty_like(x)
-    t = _t32(t)                                             # (kept alive in a local: a temporary would be freed before the launch)
-    L.check(L.lib().storm_ouve_pf_drift(L.ptr(_r(out)), L.ptr(_r(x)), L.ptr(_r(y)), L.ptr(_r(score)), L.ptr(t), x.shape[0],
-                                        _n_per_batch(x), _ouve(sde), L.stream()), "storm_ouve_pf_drift")
-    return out
-
-
 def ouve_pf_drift_g(sde, x, y, score, g_rows):
     """theta (y - x) - 1/2 g_b^2 score with the diffusion coefficient given per row (device fp32 [B])"""
     out = torch.empty_like(x)
@@ -490,13 +472,8 @@ def sde_prior_rows(y, std_rows, z=None, seed=0, offset=0, row_seeds=None):
     """y + z * std_b (OUVPSDE.prior_sampling, sdes.py:306-310); z=None draws in-kernel (Philox)."""
     x = torch.empty_like(y)
     std_rows = _rows32(std_rows, y)
-    if row_seeds is not None:
-        k = _keys(row_seeds, y)
-        L.check(L.lib().storm_sde_prior_rows_rs(L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(_r(x)), L.ptr(std_rows), y.shape[0], _n_per_batch(y),
-                                                0, offset, L.ptr(k), L.stream()), "storm_sde_prior_rows_rs")
-        return x
-    L.check(L.lib().storm_sde_prior_rows(L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(_r(x)), L.ptr(std_rows), y.shape[0], _n_per_batch(y),
-                                         seed, offset, L.stream()), "storm_sde_prior_rows")
+    _noise_call("storm_sde_prior_rows", (L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(_r(x)), L.ptr(std_rows), y.shape[0], _n_per_batch(y)),
+                seed, offset, row_seeds, y)
     return x
 
 
@@ -505,15 +482,8 @@ def sde_predictor_step_rows(sde, x, score, y, t, kind=0, z=None, noise_free=Fals
     (fp32 [B], the reference's own expressions).  In place on x; returns (x, x_mean)."""
     xm = torch.empty_like(x)
     a, g = _rows32(sde.drift_rows(t), x), _rows32(sde.diffusion(t), x)
-    if row_seeds is not None:
-        k = _keys(row_seeds, x)
-        L.check(L.lib().storm_sde_predictor_step_rows_rs(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(a),
-                                                         L.ptr(g), x.shape[0], _n_per_batch(x), int(sde.N), kind, int(noise_free), 0,
-                                                         offset, L.ptr(k), L.stream()), "storm_sde_predictor_step_rows_rs")
-        return x, xm
-    L.check(L.lib().storm_sde_predictor_step_rows(L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(a),
-                                                  L.ptr(g), x.shape[0], _n_per_batch(x), int(sde.N), kind, int(noise_free), seed,
-                                                  offset, L.stream()), "storm_sde_predictor_step_rows")
+    _noise_call("storm_sde_predictor_step_rows", (L.ptr(_r(x)), L.ptr(_r(xm)), L.ptr(_r(score)), L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(a), L.ptr(g),
+                                                  x.shape[0], _n_per_batch(x), int(sde.N), kind, int(noise_free)), seed, offset, row_seeds, x)
     return x, xm
 
 
@@ -532,30 +502,6 @@ _rk_scratch = {}
 def _kptrs(K):
     arr = (C.c_void_p * len(K))(*[L.ptr(_r(k)) for k in K])
     return arr
-
-
-def rk_combine(x, K, coef, h, out=None):
-    """out = x + h * sum_j coef[j] K[j] (one fused pass; complex64 tensors of one shape)."""
-    out = torch.empty_like(x) if out is None else out
-    cf = (C.c_float * len(K))(*[float(c) for c in coef])
-    L.check(L.lib().storm_rk_combine(L.ptr(_r(out)), L.ptr(_r(x)), _kptrs(K), cf, len(K), float(h), x.numel(), L.stream()),
-            "storm_rk_combine")
-    return out
-
-
-def rk_scaled_sumsq(xa, xb, K, coef, h, atol, rtol, mode=None):
-    """Device scalar (float64 tensor [1]) = sum over complex elements of |v|^2 / (atol + max(|xa|, |xb|) rtol)^2 with
-    v = h sum coef[j] K[j] (mode None), K[0] (mode -1) or K[0] - K[1] (mode -2); nothing is synchronised here."""
-    key = (str(xa.device), threading.get_ident())       # (per host thread: grouped micro-batches interleave their launches on one stream)
-    if key not in _rk_scratch:
-        _rk_scratch[key] = torch.empty(2048, dtype=torch.float64, device=xa.device)
-    out = torch.empty(1, dtype=torch.float64, device=xa.device)
-    n_terms = len(K) if mode is None else mode
-    cf = (C.c_float * max(1, len(K)))(*[float(c) for c in (coef if coef is not None else [0.0] * len(K))])
-    L.check(L.lib().storm_rk_scaled_sumsq(L.ptr(out), L.ptr(_rk_scratch[key]), 2048, L.ptr(_r(xa)), L.ptr(_r(xb)) if xb is not None else None,
-                                          _kptrs(K), cf, n_terms, float(h), float(atol), float(rtol), xa.numel(), L.stream()),
-            "storm_rk_scaled_sumsq")
-    return out
 
 
 RK_MAX_ROWS, RK_ROW_BLOCKS = 128, 256          # include/storm_hip.h: STORM_RK_MAX_ROWS, STORM_RK_ROW_BLOCKS
@@ -596,7 +542,7 @@ def rk_scaled_sumsq_rows(xa, xb, K, coef, h_rows, atol, rtol, mode=None):
                                                [k[i:i + RK_MAX_ROWS] for k in K], coef,
                                                h_rows[i:i + RK_MAX_ROWS] if h_rows is not None else None, atol, rtol, mode)
                           for i in range(0, B, RK_MAX_ROWS)])
-    key = (str(xa.device), "rows", threading.get_ident())
+    key = (str(xa.device), threading.get_ident())       # (per host thread: grouped micro-batches interleave their launches on one stream)
     need = RK_ROW_BLOCKS * B
     if key not in _rk_scratch or _rk_scratch[key].numel() < need:
         _rk_scratch[key] = torch.empty(need, dtype=torch.float64, device=xa.device)
@@ -621,11 +567,8 @@ def copy_rows(dst, src, mask):
 def complex_randn(shape, device, seed, offset, row_seeds=None):
     """standard complex normal noise of `shape`; with row_seeds (int64 device [shape[0]]) row b = complex_randn(shape[1:], row_seeds[b], offset)"""
     z = torch.empty(shape, dtype=torch.complex64, device=device)
-    if row_seeds is not None:
-        k = _keys(row_seeds, z)
-        L.check(L.lib().storm_complex_randn_rs(L.ptr(_r(z)), z.shape[0], _n_per_batch(z), 0, offset, L.ptr(k), L.stream()), "storm_complex_randn_rs")
-        return z
-    L.check(L.lib().storm_complex_randn(L.ptr(_r(z)), z.numel(), seed, offset, L.stream()), "storm_complex_randn")
+    rows = (z.numel(),) if row_seeds is None else (z.shape[0], _n_per_batch(z))       # (the one-seed form is ONE row of all the values)
+    _noise_call("storm_complex_randn", (L.ptr(_r(z)), *rows), seed, offset, row_seeds, z)
     return z
 
 

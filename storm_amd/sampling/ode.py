@@ -23,7 +23,6 @@ import math
 import numpy as np
 import torch
 
-from ..sdes import OUVESDE
 from .predictors import ReverseDiffusionPredictor
 
 # Dormand-Prince coefficients (scipy.integrate._ivp.rk.RK45)
@@ -80,13 +79,8 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
                 rows_evaluated += x.shape[0]
                 t_host = torch.tensor(rows(t_g), dtype=torch.float32)
                 vec_t = t_host.to(yy.device)
-                if isinstance(sde, OUVESDE):               # fused: theta (y - x) - 1/2 g^2 score in one pass; g(t) for the B
-                    score = rsde._score(x, vec_t, (y_c,), dict(conditioning=cond_c))           # rows in the reference's own ops
-                    return ops.ouve_pf_drift_g(sde, x, y_c, score.contiguous(), sde.diffusion(t_host))
-                if hasattr(sde, "drift_rows"):             # coefficient-table form (OUVPSDE): a(t_b), g(t_b) per row
-                    score = rsde._score(x, vec_t, (y_c,), dict(conditioning=cond_c))
-                    return ops.sde_pf_drift_rows(x, y_c, score.contiguous(), sde.drift_rows(t_host), sde.diffusion(t_host))
-                return rsde.sde(x, vec_t, y_c, conditioning=cond_c)[0].contiguous()
+                score = rsde._score(x, vec_t, (y_c,), dict(conditioning=cond_c))
+                return sde.pf_drift(x, y_c, score.contiguous(), t_host)      # fused: a (y - x) - 1/2 g^2 score in one pass
 
             def norms(sumsq_rows):                            # scipy: ||v|| / sqrt(size) per solver state; ONE host read
                 s = sumsq_rows.cpu().tolist()

@@ -2,7 +2,6 @@
 gives per-row coefficients: OUVPSDE) the update is one fused HIP kernel (csrc/sde.hip); the score comes from ``score_fn`` (NCSN++ engine)."""
 import abc
 
-from .. import ops
 from ..sdes import OUVESDE
 from ..util.registry import Registry
 from .noise import NoiseSource
@@ -36,11 +35,7 @@ class Predictor(abc.ABC):
         y = args[0]
         score = _score(self.score_fn, x, t, args, kwargs)
         z, keys = (None, {}) if noise_free else self.noise.draw(x)
-        if not isinstance(self.sde, OUVESDE):      # coefficient-table form: a(t_b), g(t_b) from the SDE's own fp32 expressions
-            return ops.sde_predictor_step_rows(self.sde, x.contiguous(), score.contiguous(), y.contiguous(), t.contiguous(),
-                                               kind=kind, z=z, noise_free=noise_free, **keys)
-        return ops.ouve_predictor_step(self.sde, x.contiguous(), score.contiguous(), y.contiguous(), t.contiguous(),
-                                       kind=kind, z=z, noise_free=noise_free, **keys)
+        return self.sde.predictor_step(x.contiguous(), score.contiguous(), y.contiguous(), t.contiguous(), kind, z=z, noise_free=noise_free, **keys)
 
 
 @PredictorRegistry.register("euler_maruyama")

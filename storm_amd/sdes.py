@@ -57,6 +57,17 @@ class SDE(abc.ABC):
         G = diffusion * torch.sqrt(torch.tensor(dt, device=t.device))
         return f, G
 
+    # The fused steps of the samplers (csrc/sde.hip).  These are the coefficient-table forms, for any SDE with a linear drift
+    # a(t) (y - x) that gives a(t_b), g(t_b) per row as `drift_rows(t)` / `diffusion(t)` in its own fp32 expressions (OUVPSDE);
+    # OUVESDE overrides them with the forms that take its parameters.
+    def predictor_step(self, x, score, y, t, kind, z=None, noise_free=False, **keys):
+        """one predictor update (kind 0 reverse diffusion, 1 Euler-Maruyama), in place on x; returns (x, x_mean)"""
+        return ops.sde_predictor_step_rows(self, x, score, y, t, kind=kind, z=z, noise_free=noise_free, **keys)
+
+    def pf_drift(self, x, y, score, t_host):
+        """the probability-flow right-hand side a(t_b) (y - x) - 1/2 g(t_b)^2 score (t_host: fp32 [B] on the host)"""
+        return ops.sde_pf_drift_rows(x, y, score, self.drift_rows(t_host), self.diffusion(t_host))
+
     def reverse(oself, score_model, probability_flow=False, diffusion_power_gradient=None):
         """Reverse-time SDE/ODE (sdes.py:92-159).  diffusion_power_gradient(x, t): subtracted from the total drift when the
         diffusion depends on the state (sdes.py:98-99, 137-138); None for both registered SDEs."""
@@ -146,6 +157,14 @@ class OUVESDE(SDE):
             warnings.warn(f"Target shape {shape} does not match shape of y {y.shape}! Ignoring target shape.")
         return ops.ouve_prior(self, y.contiguous(), z=z, seed=seed, offset=offset, row_seeds=row_seeds)
 
+    def predictor_step(self, x, score, y, t, kind, z=None, noise_free=False, **keys):
+        """g(t_b) is computed in-kernel from t (fp64, rounded once)"""
+        return ops.ouve_predictor_step(self, x, score, y, t, kind=kind, z=z, noise_free=noise_free, **keys)
+
+    def pf_drift(self, x, y, score, t_host):
+        """theta (y - x) - 1/2 g(t_b)^2 score; g(t) for the B rows in the reference's own torch ops"""
+        return ops.ouve_pf_drift_g(self, x, y, score, self.diffusion(t_host))
+
     def prior_logp(self, z):
         raise NotImplementedError("prior_logp for OU SDE not yet implemented!")
 
@@ -163,9 +182,10 @@ class OUVPSDE(SDE):
     """Ornstein-Uhlenbeck variance-preserving SDE  dx = 1/2 beta(t) stiffness (y - x) dt + sqrt(beta(t)) dw,
     beta(t) = beta_min + t (beta_max - beta_min)  (sdes.py:255-326).
 
-    The samplers reach it through `drift_rows(t)` / `diffusion(t)`: the per-row coefficients a(t_b), g(t_b) in the reference's
-    own fp32 expressions, handed to the coefficient-table kernels (storm_sde_*_rows).  As upstream, the `ald` corrector
-    rejects it (correctors.py:69); `langevin` / `none` and both predictors and the ODE sampler take it."""
+    The samplers reach it through the base class's `predictor_step` / `pf_drift`, which hand `drift_rows(t)` / `diffusion(t)` - the
+    per-row coefficients a(t_b), g(t_b) in the reference's own fp32 expressions - to the coefficient-table kernels
+    (storm_sde_*_rows).  As upstream, the `ald` corrector rejects it (correctors.py:69); `langevin` / `none` and both predictors
+    and the ODE sampler take it."""
 
     def __init__(self, beta_min, beta_max, stiffness=1, N=1000, **ignored_kwargs):
         super().__init__(N)

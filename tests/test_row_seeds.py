@@ -90,6 +90,31 @@ def test_kernel_rows_equal_their_batch1_calls(dev, name, B, n, offset):
         assert not torch.equal(batched[0][0], batched[0][1])
 
 
+def test_row_longer_than_the_grid_takes_the_stride_loop(dev):
+    """The row launch caps at 2048 blocks of 256 threads: a row of 2048 * 256 + 7 elements sends the first 7 threads round the
+    grid-stride loop a second time (no other case has a row that long).  The updates are elementwise and the noise is injected,
+    so nothing depends on an element's position: the call on the whole row is BIT-equal to the same call on the first
+    2048 * 256 elements and on the 7-element tail."""
+    from storm_amd import ops
+    from storm_amd.sdes import OUVESDE, OUVPSDE
+    sde, psde = OUVESDE(1.5, 0.05, 0.5, N=30), OUVPSDE(0.1, 2.0, 1, N=30)
+    head = 2048 * 256
+    ins = _inputs(1, head + 7, dev)
+    ins["z"] = torch.view_as_complex(torch.randn(1, head + 7, 2, generator=torch.Generator().manual_seed(5))).to(dev)
+    t = ins["t"]
+    calls = {
+        "ouve_prior": lambda i: (ops.ouve_prior(sde, i["y"], z=i["z"]),),
+        "ouve_predictor_step": lambda i: ops.ouve_predictor_step(sde, i["x"].clone(), i["score"], i["y"], t, kind=0, z=i["z"]),
+        "sde_predictor_step_rows": lambda i: ops.sde_predictor_step_rows(psde, i["x"].clone(), i["score"], i["y"], t, kind=0, z=i["z"]),
+        "sde_pf_drift_rows": lambda i: (ops.sde_pf_drift_rows(i["x"], i["y"], i["score"], psde.drift_rows(t), psde.diffusion(t)),),
+    }
+    parts = [{k: v[:, sl].contiguous() for k, v in ins.items() if k != "t"} for sl in (slice(None, head), slice(head, None))]
+    for name, fn in calls.items():
+        whole, first, tail = fn(ins), fn(parts[0]), fn(parts[1])
+        for w, a, b in zip(whole, first, tail):
+            assert w.shape == (1, head + 7) and torch.equal(w, torch.cat([a, b], 1)), name
+
+
 # ---------------------------------------------------------------- samplers and models (tiny nets, F = 256, one 64-frame bucket, N = 3)
 def _ouvp_model(dev):
     from storm_amd.data_module import SpecsDataModule
