@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include "common.h"
 
 namespace storm {
@@ -209,16 +210,17 @@ __device__ __forceinline__ void gather8(const T* xa, int Ca, const T* xb, int Cb
     }
 }
 
+// GN-apply (+ SiLU) without resampling.  RESAMPLE is 0 (the resampling members are the strip walkers below); the argument stays in the
+// kernel's name, which profiles and tools match
 template <typename T, int RESAMPLE>
 __global__ void gn_apply_kernel(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb,
                                 int H, int W, int G, const double* __restrict__ stats,
                                 const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                 int silu, T* __restrict__ out_act, T* __restrict__ out_raw,
                                 int ppb, int C8, int PL) {
+    static_assert(RESAMPLE == 0, "gn_apply_kernel: no resampling");
     const int C = Ca + Cb, b = blockIdx.y, tid = threadIdx.x;
     const int oct = tid % C8, pl = tid / C8, c = oct * 8;
-    const int OH = RESAMPLE == 1 ? 2 * H : (RESAMPLE == 2 ? H / 2 : H);
-    const int OW = RESAMPLE == 1 ? 2 * W : (RESAMPLE == 2 ? W / 2 : W);
     const int gs = C / G;
     const double n = (double)gs * H * W;
     GnParams gp;
@@ -233,288 +235,233 @@ __global__ void gn_apply_kernel(const T* __restrict__ xa, int Ca, const T* __res
         gp.a[e] = rstd * gamma[c + e];
         gp.beta[e] = beta[c + e];
     }
-    const long long ibase = (long long)b * H * W, obase = (long long)b * OH * OW;
-    const int OHW = OH * OW;
-    const int p0 = blockIdx.x * ppb, p1 = min(OHW, p0 + ppb);
+    const long long base = (long long)b * H * W;
+    const int HW = H * W;
+    const int p0 = blockIdx.x * ppb, p1 = min(HW, p0 + ppb);
     for (int p = p0 + pl; p < p1; p += PL) {
-        const int oy = p / OW, ox = p - oy * OW;
+        const int oy = p / W, ox = p - oy * W;
         float v[8];
-        gather8<T, RESAMPLE, true>(xa, Ca, xb, Cb, ibase, H, W, oy, ox, c, gp, silu, v);
-        store8(out_act + (obase + p) * C + c, v);
-        if (RESAMPLE != 0 && out_raw != nullptr) {
-            gather8<T, RESAMPLE, false>(xa, Ca, xb, Cb, ibase, H, W, oy, ox, c, gp, 0, v);
-            store8(out_raw + (obase + p) * C + c, v);
-        }
+        gather8<T, 0, true>(xa, Ca, xb, Cb, base, H, W, oy, ox, c, gp, silu, v);
+        store8(out_act + (base + p) * C + c, v);
     }
 }
 
-// Fused GN-apply + SiLU + FIR x2 DOWN of both the activated and the raw tensor, register sliding window (no LDS tile, no
-// barriers in the loop).  The separable filter k = [1,3,3,1] / 8 per axis, out[oy][ox] = sum_i k_i (sum_j k_j x[2 oy - 1 + i][2 ox - 1 + j]):
-// a thread owns one 16-byte channel slot of one output column and walks DOWN a strip of output rows; per output row it loads
-// the four taps of two new input rows (16 B each: the loaded slot feeds both tensors), normalises + activates them once,
-// filters each row horizontally with v_dot2c on the packed 16-bit data, and combines with the carry of the two rows it shares
-// with the previous output row (out[oy] = carry + k2 h[2 oy + 1] + k3 h[2 oy + 2]; carry' = k0 h[2 oy + 1] + k1 h[2 oy + 2]).
-// Workgroup = 8 slots (128 B per pixel: coalesced loads and stores) x 32 output columns; ~80 registers, so 5-6 waves per SIMD
-// keep 8 KiB of loads in flight each - the LDS-tiled predecessor (10 x 18-pixel tiles staged once, 3 workgroups per CU, two
-// barriers per 32 output pixels; git show 9dfa6dc:storm_amd/csrc/norm_resample.hip) ran at 1.7 TB/s with its waves parked half
-// of the time (profiles/r03a_pmc_summary.txt); this one measures 2.8 TB/s.
-constexpr int DN_ROWS = 16;                         // output rows per strip
-// NS = 16-byte slots of a pixel per workgroup (256 / NS output columns).  Round 3 used 8 everywhere (one 128-byte line per pixel and
+// ---- the strip walkers: GN-apply (+ SiLU) + x2 resampling of BOTH the activated and the raw tensor in one pass -------------------------------
+// A thread owns one 16-byte channel slot of one column and walks down a strip of rows: it normalises + activates what it loads, resamples
+// the activated and the raw tensor and writes both.  The four kernels (FIR down, barrier-free or with the activation shared through LDS; FIR
+// up; the non-FIR nearest / mean pair) differ in the resampling only; what follows is what they have in common.
+constexpr int GN_STRIP_ROWS = 16;                   // rows per strip (input rows up, output rows down; gn_strips shortens them for small calls)
+// NS = 16-byte slots of a pixel per workgroup (256 / NS columns).  Round 3 used 8 everywhere (one 128-byte line per pixel and
 // wave access); with NS = 32 a wave reads / writes 512 contiguous bytes per pixel - whole DRAM bursts of one page instead of 128-byte
 // pieces 1 KiB apart that other workgroups complete at another time (round 4: the write stream of the up-sampling kernel was at 4.1 TB/s
 // where a plain fill reaches 6.9, profiles/r04f_hbm_probe.txt).
 // SILU: the activation as a compile-time choice (as a run-time flag it is if-converted: both results computed, a select per value)
-template <typename T, bool SILU, int NS>
-__device__ __forceinline__ void gn_apply_down_body(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb,
-                          int H, int W, int G, const double* __restrict__ stats,
-                          const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                          T* __restrict__ out_act, T* __restrict__ out_raw, int ncg, int nstrips, int nt_stores, const int by, const int bx) {
-    constexpr int PER16 = Elem<T>::PER16;
-    constexpr int CG = NS * PER16;                  // channels per workgroup
-    constexpr int DN_COLS = 256 / NS;               // output columns per workgroup
-    __shared__ float gtab[2 * CG];
-    const int C = Ca + Cb, tid = threadIdx.x;
-    const int slot = tid % NS, col = tid / NS;
-    const int OH = H / 2, OW = W / 2;
-    int t = by;                             // (channel group, strip, batch item)
-    const int cg = t % ncg; t /= ncg;
-    const int strip = t % nstrips, b = t / nstrips;
-    const int gs = C / G;
-    if (tid < CG) {                                 // (scale, shift) of this workgroup's channels: y = x * sc + sh
-        const int cc = cg * CG + tid;
-        float sc = 0.f, sh = 0.f;
-        if (cc < C) {
-            const double n = (double)gs * H * W;
-            const int g = cc / gs;
-            const double m = stats[((long long)b * G + g) * 2] / n;
-            double var = stats[((long long)b * G + g) * 2 + 1] / n - m * m;
-            if (var < 0.0) var = 0.0;
-            const float pm = (float)m;
-            sc = (float)(1.0 / sqrt(var + (double)eps)) * gamma[cc];
-            sh = beta[cc] - pm * sc;
-        }
-        gtab[2 * tid] = sc; gtab[2 * tid + 1] = sh;
-    }
-    __syncthreads();
-    const int c = cg * CG + slot * PER16;
-    const int ox = bx * DN_COLS + col;
-    if (c >= C || ox >= OW) return;
-    float pa[PER16], pb[PER16];
-#pragma unroll
-    for (int e = 0; e < PER16; ++e) { pa[e] = gtab[2 * (slot * PER16 + e)]; pb[e] = gtab[2 * (slot * PER16 + e) + 1]; }
-    const T* const src = (c < Ca) ? xa + c : xb + (c - Ca);
-    const int cs = (c < Ca) ? Ca : Cb;              // channel stride of the source this slot lives in
-    const long long ibase = (long long)b * H * W;
-    const long long obase = (long long)b * OH * OW;
-    const int ix0 = 2 * ox - 1;
-    const bool x_in[4] = {ix0 >= 0, true, ix0 + 2 < W, ix0 + 3 < W};     // (ix0 + 1 = 2 ox < W always)
 
-    // the horizontally filtered input row iy, activated (hA) and raw (hR): zero rows / taps outside the image
-    auto hrow = [&](int iy, float (&hA)[PER16], float (&hR)[PER16]) {
-#pragma unroll
-        for (int e = 0; e < PER16; ++e) { hA[e] = 0.f; hR[e] = 0.f; }
-        if (iy < 0 || iy >= H) return;
-        const T* const row = src + (ibase + (long long)iy * W) * cs;
-        uint4 q[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            q[j] = x_in[j] ? *reinterpret_cast<const uint4*>(row + (long long)(ix0 + j) * cs) : make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float wgt = (j == 0 || j == 3) ? 0.125f : 0.375f;
-            alignas(16) T raw[PER16];
-            *reinterpret_cast<uint4*>(raw) = q[j];
-            if constexpr (sizeof(T) == 2) {
-                uint32_t aw[4] = {0u, 0u, 0u, 0u};
-                if (x_in[j]) {
-#pragma unroll
-                    for (int e = 0; e < PER16; e += 2) {
-                        f32x2 y = __builtin_elementwise_fma(f32x2{to_f32(raw[e]), to_f32(raw[e + 1])}, f32x2{pa[e], pa[e + 1]}, f32x2{pb[e], pb[e + 1]});
-                        if (SILU) y = silu2(y);
-                        aw[e / 2] = pack2(y.x, y.y, (T*)nullptr);
-                    }
-                }
-                uint32_t wl = tap_weight_bits(wgt, (T*)nullptr), wh = wl << 16;
-                keep_rw(wl); keep_rw(wh);            // (packed 16-bit operands of v_dot2c must come from registers: see above)
-                const uint32_t r[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    hA[2 * i] = dot2_acc(aw[i], wl, hA[2 * i], (T*)nullptr); hA[2 * i + 1] = dot2_acc(aw[i], wh, hA[2 * i + 1], (T*)nullptr);
-                    hR[2 * i] = dot2_acc(r[i], wl, hR[2 * i], (T*)nullptr); hR[2 * i + 1] = dot2_acc(r[i], wh, hR[2 * i + 1], (T*)nullptr);
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < PER16; ++e) {
-                    const float xr = to_f32(raw[e]);
-                    float y = 0.f;
-                    if (x_in[j]) {
-                        y = fmaf(xr, pa[e], pb[e]);
-                        if (SILU) y = silu_f(y);
-                        T ya; from_f32(ya, y); y = to_f32(ya);      // (the activated tensor is rounded to T before it is filtered)
-                    }
-                    hA[e] = fmaf(wgt, y, hA[e]); hR[e] = fmaf(wgt, xr, hR[e]);
-                }
+// What every workgroup starts with: by (blockIdx.y, or a grouped launch's item) = (channel group, strip, batch item); the (scale,
+// shift) of the workgroup's channels, y = x * sc + sh, from the fp64 statistics through LDS to the lanes that own them; a lane's slot lives
+// in xa or in xb (cat[h, skip] of the up blocks is never materialised).
+template <typename T, int NS>
+struct GnLane {
+    static constexpr int PER16 = Elem<T>::PER16;
+    static constexpr int CG = NS * PER16;           // channels per workgroup
+    static constexpr int COLS = 256 / NS;           // columns per workgroup
+    int slot, col, strip, b, c;
+    bool chan;                                      // false: a slot past a ragged last channel group (it loads and stores nothing; src is channel 0's)
+    float pa[PER16], pb[PER16];                     // scale, shift of the slot's channels
+    const T* src;                                   // the slot in pixel 0 of the source it lives in
+    int cs;                                         // channel stride of that source
+    long long ibase;                                // first pixel of the batch item
+    __device__ __forceinline__ GnLane(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb, int H, int W, int G,
+                                      const double* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                      int ncg, int nstrips, int by) {
+        __shared__ float gtab[2 * CG];
+        const int C = Ca + Cb, tid = threadIdx.x;
+        slot = tid % NS; col = tid / NS;
+        int t = by;                                 // (channel group, strip, batch item)
+        const int cg = t % ncg; t /= ncg;
+        strip = t % nstrips; b = t / nstrips;
+        const int gs = C / G;
+        if (tid < CG) {                             // (scale, shift) of this workgroup's channels: y = x * sc + sh
+            const int cc = cg * CG + tid;
+            float sc = 0.f, sh = 0.f;
+            if (cc < C) {
+                const double n = (double)gs * H * W;
+                const int g = cc / gs;
+                const double m = stats[((long long)b * G + g) * 2] / n;
+                double var = stats[((long long)b * G + g) * 2 + 1] / n - m * m;
+                if (var < 0.0) var = 0.0;
+                const float pm = (float)m;
+                sc = (float)(1.0 / sqrt(var + (double)eps)) * gamma[cc];
+                sh = beta[cc] - pm * sc;
             }
+            gtab[2 * tid] = sc; gtab[2 * tid + 1] = sh;
         }
-    };
-    const int dn_rows = (OH + nstrips - 1) / nstrips;
-    const int oy0 = strip * dn_rows, oy1 = min(OH, oy0 + dn_rows);
-    float cA[PER16], cR[PER16];                     // carry: k0 h[2 oy - 1] + k1 h[2 oy]
-    {
-        float h0A[PER16], h0R[PER16], h1A[PER16], h1R[PER16];
-        hrow(2 * oy0 - 1, h0A, h0R);
-        hrow(2 * oy0, h1A, h1R);
+        __syncthreads();
+        c = cg * CG + slot * PER16;
+        chan = c < C;
 #pragma unroll
-        for (int e = 0; e < PER16; ++e) { cA[e] = fmaf(0.375f, h1A[e], 0.125f * h0A[e]); cR[e] = fmaf(0.375f, h1R[e], 0.125f * h0R[e]); }
+        for (int e = 0; e < PER16; ++e) { pa[e] = gtab[2 * (slot * PER16 + e)]; pb[e] = gtab[2 * (slot * PER16 + e) + 1]; }
+        const int cl = chan ? c : 0;
+        src = (cl < Ca) ? xa + cl : xb + (cl - Ca);
+        cs = (cl < Ca) ? Ca : Cb;
+        ibase = (long long)b * H * W;
     }
-    for (int oy = oy0; oy < oy1; ++oy) {
-        float h2A[PER16], h2R[PER16], h3A[PER16], h3R[PER16];
-        hrow(2 * oy + 1, h2A, h2R);
-        hrow(2 * oy + 2, h3A, h3R);
-        float va[PER16], vr[PER16];
-#pragma unroll
-        for (int e = 0; e < PER16; ++e) {
-            va[e] = fmaf(0.125f, h3A[e], fmaf(0.375f, h2A[e], cA[e]));
-            vr[e] = fmaf(0.125f, h3R[e], fmaf(0.375f, h2R[e], cR[e]));
-            cA[e] = fmaf(0.375f, h3A[e], 0.125f * h2A[e]);
-            cR[e] = fmaf(0.375f, h3R[e], 0.125f * h2R[e]);
-        }
-        const long long o = (obase + (long long)oy * OW + ox) * C + c;
-        if constexpr (sizeof(T) == 2) {
-            const uint4 qa = make_uint4(pack2(va[0], va[1], (T*)nullptr), pack2(va[2], va[3], (T*)nullptr),
-                                        pack2(va[4], va[5], (T*)nullptr), pack2(va[6], va[7], (T*)nullptr));
-            const uint4 qr = make_uint4(pack2(vr[0], vr[1], (T*)nullptr), pack2(vr[2], vr[3], (T*)nullptr),
-                                        pack2(vr[4], vr[5], (T*)nullptr), pack2(vr[6], vr[7], (T*)nullptr));
-            if (nt_stores) { store16_nt(out_act + o, qa); if (out_raw) store16_nt(out_raw + o, qr); }
-            else { *reinterpret_cast<uint4*>(out_act + o) = qa; if (out_raw) *reinterpret_cast<uint4*>(out_raw + o) = qr; }
-        } else {
-            alignas(16) T oa[PER16];
-            alignas(16) T orr[PER16];
-#pragma unroll
-            for (int e = 0; e < PER16; ++e) { from_f32(oa[e], va[e]); from_f32(orr[e], vr[e]); }
-            *reinterpret_cast<uint4*>(out_act + o) = *reinterpret_cast<const uint4*>(oa);
-            if (out_raw) *reinterpret_cast<uint4*>(out_raw + o) = *reinterpret_cast<const uint4*>(orr);
-        }
-    }
-}
-template <typename T, bool SILU, int NS>
-__global__ __launch_bounds__(256)
-void gn_apply_down_kernel(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb, int H, int W, int G, const double* __restrict__ stats,
-          const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* __restrict__ out_act, T* __restrict__ out_raw,
-          int ncg, int nstrips, int nt_stores) {
-    gn_apply_down_body<T, SILU, NS>(xa, Ca, xb, Cb, H, W, G, stats, gamma, beta, eps, out_act, out_raw, ncg, nstrips, nt_stores, blockIdx.y, blockIdx.x);
-}
-// the strips of SEVERAL problems in one launch (grouped evaluation of a ragged stream's micro-batches, common.h): blockIdx.y = an item
-// (problem, the y index of the problem's own launch) of a host-built list; a strip is computed by the code of its own launch
-template <typename T, bool SILU, int NS>
-__global__ __launch_bounds__(256)
-void gn_apply_down_group_kernel(const GnApplyProblem* __restrict__ tab, const GnFinItem* __restrict__ items, int Ca, int Cb, int G,
-           const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int nt_stores) {
-    const GnFinItem it = items[blockIdx.y];
-    const GnApplyProblem& q = tab[it.problem];
-    if ((int)blockIdx.x >= q.cols) return;
-    gn_apply_down_body<T, SILU, NS>(static_cast<const T*>(q.xa), Ca, static_cast<const T*>(q.xb), Cb, q.H, q.W, G, q.stats, gamma, beta, eps,
-                      static_cast<T*>(q.out_act), static_cast<T*>(q.out_raw), q.ncg, q.nstrips, nt_stores, it.b, blockIdx.x);
-}
+};
 
-// Round 5: the down-sampling kernel with the ACTIVATION shared between neighbouring threads.  Timed without its SiLU the kernel above runs at the
-// memory time (169 of 280 us at the bench batch's level-0 launch, tools/debug/probe_gn_silu.py): it is bound by the activation - two quarter-rate
-// transcendentals per element - and evaluates it TWICE per input pixel, because the four taps of neighbouring output columns overlap by two.  Here a
-// thread still loads its four taps (the raw tensor's filter needs them) but normalises + activates only the two centre columns it owns (2 ox,
-// 2 ox + 1), hands them to its neighbours through LDS and takes its outer taps from theirs; the first / last column of a workgroup activates its
-// outer tap itself (one masked pass in the two edge waves).  5 activation passes per output row and wave on average instead of 8; one barrier per
-// output row (double-buffered exchange); every activated value is computed by the same arithmetic from the same inputs whoever computes it, and
-// each output keeps its own tap order: the same bits (test_groupnorm_fir_fused).  Wider register windows instead (two output columns per thread)
-// paid the saved instructions back in occupancy: tools/experiments/gn_down_two_columns.patch.
-template <typename T, bool SILU, int NS>
-__device__ __forceinline__ void gn_apply_down_share_body(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb,
-                                int H, int W, int G, const double* __restrict__ stats,
-                                const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                T* __restrict__ out_act, T* __restrict__ out_raw, int ncg, int nstrips, int nt_stores, const int by, const int bx) {
+// GroupNorm affine (+ SiLU) of one 16-byte slot, rounded to T (the activated tensor is rounded to T before it is filtered); ok = false:
+// zeros (a tap outside the image)
+template <typename T, bool SILU>
+__device__ __forceinline__ uint4 gn_activate(const uint4 q, const bool ok, const float (&pa)[Elem<T>::PER16], const float (&pb)[Elem<T>::PER16]) {
     constexpr int PER16 = Elem<T>::PER16;
-    constexpr int CG = NS * PER16;                  // channels per workgroup
-    constexpr int DN_COLS = 256 / NS;               // output columns per workgroup
-    constexpr int LC = 2 * DN_COLS + 2;             // local input columns 0 .. LC - 1 = taps 2 col + j (0 and LC - 1: the edge threads' own)
-    __shared__ float gtab[2 * CG];
-    __shared__ uint4 xact[2][2][LC][NS];            // [exchange buffer][row of the pair][local input column][slot]: activated, in T
-    const int C = Ca + Cb, tid = threadIdx.x;
-    const int slot = tid % NS, col = tid / NS;
-    const int OH = H / 2, OW = W / 2;
-    int t = by;                             // (channel group, strip, batch item)
-    const int cg = t % ncg; t /= ncg;
-    const int strip = t % nstrips, b = t / nstrips;
-    const int gs = C / G;
-    if (tid < CG) {                                 // (scale, shift) of this workgroup's channels: y = x * sc + sh
-        const int cc = cg * CG + tid;
-        float sc = 0.f, sh = 0.f;
-        if (cc < C) {
-            const double n = (double)gs * H * W;
-            const int g = cc / gs;
-            const double m = stats[((long long)b * G + g) * 2] / n;
-            double var = stats[((long long)b * G + g) * 2 + 1] / n - m * m;
-            if (var < 0.0) var = 0.0;
-            const float pm = (float)m;
-            sc = (float)(1.0 / sqrt(var + (double)eps)) * gamma[cc];
-            sh = beta[cc] - pm * sc;
-        }
-        gtab[2 * tid] = sc; gtab[2 * tid + 1] = sh;
-    }
-    __syncthreads();
-    const int c = cg * CG + slot * PER16;
-    const int ox = bx * DN_COLS + col;
-    const bool chan = c < C;                        // (a slot past a ragged last channel group loads nothing - but every thread takes part in the barriers)
-    const bool live = chan && ox < OW;              // (a column past the image may still own input columns a live neighbour filters)
-    float pa[PER16], pb[PER16];
-#pragma unroll
-    for (int e = 0; e < PER16; ++e) { pa[e] = gtab[2 * (slot * PER16 + e)]; pb[e] = gtab[2 * (slot * PER16 + e) + 1]; }
-    const int cl = chan ? c : 0;
-    const T* const src = (cl < Ca) ? xa + cl : xb + (cl - Ca);
-    const int cs = (cl < Ca) ? Ca : Cb;             // channel stride of the source this slot lives in
-    const long long ibase = (long long)b * H * W;
-    const long long obase = (long long)b * OH * OW;
-    const int ix0 = 2 * ox - 1;
-    bool x_in[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x_in[j] = chan && ix0 + j >= 0 && ix0 + j < W;
-    const bool first = col == 0, last = col == DN_COLS - 1;
-
-    auto activate = [&](const uint4 qv, bool ok) -> uint4 {          // GroupNorm affine (+ SiLU) of one 16-byte slot, rounded to T
-        uint4 r = make_uint4(0u, 0u, 0u, 0u);
-        if (!ok) return r;
-        alignas(16) T raw[PER16];
-        *reinterpret_cast<uint4*>(raw) = qv;
-        if constexpr (sizeof(T) == 2) {
-            uint32_t aw[4];
+    alignas(16) T raw[PER16];
+    *reinterpret_cast<uint4*>(raw) = q;
+    if constexpr (sizeof(T) == 2) {
+        uint32_t aw[4] = {0u, 0u, 0u, 0u};
+        if (ok) {
 #pragma unroll
             for (int e = 0; e < PER16; e += 2) {
                 f32x2 y = __builtin_elementwise_fma(f32x2{to_f32(raw[e]), to_f32(raw[e + 1])}, f32x2{pa[e], pa[e + 1]}, f32x2{pb[e], pb[e + 1]});
                 if (SILU) y = silu2(y);
                 aw[e / 2] = pack2(y.x, y.y, (T*)nullptr);
             }
-            r = make_uint4(aw[0], aw[1], aw[2], aw[3]);
-        } else {
-            alignas(16) T ya[PER16];
+        }
+        return make_uint4(aw[0], aw[1], aw[2], aw[3]);
+    } else {
+        alignas(16) T ya[PER16];
+#pragma unroll
+        for (int e = 0; e < PER16; ++e) from_f32(ya[e], 0.f);
+        if (ok) {
 #pragma unroll
             for (int e = 0; e < PER16; ++e) {
                 float y = fmaf(to_f32(raw[e]), pa[e], pb[e]);
                 if (SILU) y = silu_f(y);
-                from_f32(ya[e], y);                 // (the activated tensor is rounded to T before it is filtered)
+                from_f32(ya[e], y);
             }
-            r = *reinterpret_cast<const uint4*>(ya);
         }
-        return r;
-    };
-    // raw taps of input row iy (zeros outside the image)
-    auto load_row = [&](int iy, uint4 (&q)[4]) {
+        return *reinterpret_cast<const uint4*>(ya);
+    }
+}
+// one filter tap on a slot of both tensors: hA += w * a (activated), hR += w * q (raw).  16-bit data stay packed: v_dot2c with the weight
+// in one half of the second operand (hw.h: dot2_acc) - the same value as the fmaf of the fp32 path
+template <typename T>
+__device__ __forceinline__ void gn_tap(const float w, const uint4 a, const uint4 q, float (&hA)[Elem<T>::PER16], float (&hR)[Elem<T>::PER16]) {
+    constexpr int PER16 = Elem<T>::PER16;
+    if constexpr (sizeof(T) == 2) {
+        uint32_t wl = tap_weight_bits(w, (T*)nullptr), wh = wl << 16;
+        keep_rw(wl); keep_rw(wh);                   // (a packed 16-bit operand of v_dot2c must come from a register: as a 32-bit literal only its low half is honoured, hw.h)
+        const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, rw[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            hA[2 * i] = dot2_acc(aw[i], wl, hA[2 * i], (T*)nullptr); hA[2 * i + 1] = dot2_acc(aw[i], wh, hA[2 * i + 1], (T*)nullptr);
+            hR[2 * i] = dot2_acc(rw[i], wl, hR[2 * i], (T*)nullptr); hR[2 * i + 1] = dot2_acc(rw[i], wh, hR[2 * i + 1], (T*)nullptr);
+        }
+    } else {
+        alignas(16) T ya[PER16];
+        alignas(16) T xr[PER16];
+        *reinterpret_cast<uint4*>(ya) = a;
+        *reinterpret_cast<uint4*>(xr) = q;
+#pragma unroll
+        for (int e = 0; e < PER16; ++e) { hA[e] = fmaf(w, to_f32(ya[e]), hA[e]); hR[e] = fmaf(w, to_f32(xr[e]), hR[e]); }
+    }
+}
+// the four-tap horizontal filter k = [1,3,3,1] / 8 of one row: activated (hA) and raw (hR), taps in the order 0 .. 3; act(j) = the
+// activated tap j (taken where it is filtered: a caller that computes it there keeps one tap live, not four)
+template <typename T, typename Act>
+__device__ __forceinline__ void gn_hfilter4(Act&& act, const uint4 (&q)[4], float (&hA)[Elem<T>::PER16], float (&hR)[Elem<T>::PER16]) {
+#pragma unroll
+    for (int e = 0; e < Elem<T>::PER16; ++e) { hA[e] = 0.f; hR[e] = 0.f; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gn_tap<T>((j == 0 || j == 3) ? 0.125f : 0.375f, act(j), q[j], hA, hR);
+}
+// a slot's values rounded to T ...
+template <typename T>
+__device__ __forceinline__ uint4 gn_pack(const float (&v)[Elem<T>::PER16]) {
+    if constexpr (sizeof(T) == 2) {
+        return pack8<T>(v);
+    } else {
+        alignas(16) T ov[Elem<T>::PER16];
+#pragma unroll
+        for (int e = 0; e < Elem<T>::PER16; ++e) from_f32(ov[e], v[e]);
+        return *reinterpret_cast<const uint4*>(ov);
+    }
+}
+// ... and stored: non-temporally (outputs far larger than the L2 that nobody reads soon, STORM_GN_NT) or plainly
+template <typename T>
+__device__ __forceinline__ void gn_put(T* dst, const uint4 q, int nt) {
+    if (nt) store16_nt(dst, q);
+    else *reinterpret_cast<uint4*>(dst) = q;
+}
+// the strips of SEVERAL problems in one launch (grouped evaluation of a ragged stream's micro-batches, common.h): blockIdx.y = an item
+// (problem, the y index of the problem's own launch) of a host-built list; a strip is computed by the code (`body`) of its own launch
+template <typename T, typename Body>
+__device__ __forceinline__ void gn_apply_group_item(const GnApplyProblem* __restrict__ tab, const GnFinItem* __restrict__ items, int Ca, int Cb, int G,
+           const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int nt_stores, Body body) {
+    const GnFinItem it = items[blockIdx.y];
+    const GnApplyProblem& q = tab[it.problem];
+    if ((int)blockIdx.x >= q.cols) return;
+    body(static_cast<const T*>(q.xa), Ca, static_cast<const T*>(q.xb), Cb, q.H, q.W, G, q.stats, gamma, beta, eps,
+         static_cast<T*>(q.out_act), static_cast<T*>(q.out_raw), q.ncg, q.nstrips, nt_stores, it.b, (int)blockIdx.x);
+}
+
+// Fused GN-apply + SiLU + FIR x2 DOWN of both the activated and the raw tensor, register sliding window (no LDS tile).  The separable
+// filter k = [1,3,3,1] / 8 per axis, out[oy][ox] = sum_i k_i (sum_j k_j x[2 oy - 1 + i][2 ox - 1 + j]):
+// a thread owns one 16-byte channel slot of one output column and walks DOWN a strip of output rows; per output row it loads
+// the four taps of two new input rows (16 B each: the loaded slot feeds both tensors), normalises + activates them once,
+// filters each row horizontally with v_dot2c on the packed 16-bit data, and combines with the carry of the two rows it shares
+// with the previous output row (out[oy] = carry + k2 h[2 oy + 1] + k3 h[2 oy + 2]; carry' = k0 h[2 oy + 1] + k1 h[2 oy + 2]).
+// SHARE = false (gn_apply_down_kernel): no barriers in the loop, a thread activates its four taps itself.
+// Workgroup = 8 slots (128 B per pixel: coalesced loads and stores) x 32 output columns; ~80 registers, so 5-6 waves per SIMD
+// keep 8 KiB of loads in flight each - the LDS-tiled predecessor (10 x 18-pixel tiles staged once, 3 workgroups per CU, two
+// barriers per 32 output pixels; git show 9dfa6dc:storm_amd/csrc/norm_resample.hip) ran at 1.7 TB/s with its waves parked half
+// of the time (profiles/r03a_pmc_summary.txt); this one measures 2.8 TB/s.
+// SHARE = true (gn_apply_down_share_kernel), round 5: the ACTIVATION shared between neighbouring threads.  Timed without its SiLU the kernel above
+// runs at the memory time (169 of 280 us at the bench batch's level-0 launch, tools/debug/probe_gn_silu.py): it is bound by the activation - two
+// quarter-rate transcendentals per element - and evaluates it TWICE per input pixel, because the four taps of neighbouring output columns overlap by
+// two.  Here a thread still loads its four taps (the raw tensor's filter needs them) but normalises + activates only the two centre columns it owns
+// (2 ox, 2 ox + 1), hands them to its neighbours through LDS and takes its outer taps from theirs; the first / last column of a workgroup activates
+// its outer tap itself (one masked pass in the two edge waves).  5 activation passes per output row and wave on average instead of 8; one barrier per
+// output row (double-buffered exchange); every activated value is computed by the same arithmetic from the same inputs whoever computes it, and
+// each output keeps its own tap order: the same bits (test_groupnorm_fir_fused).  Wider register windows instead (two output columns per thread)
+// paid the saved instructions back in occupancy: tools/experiments/gn_down_two_columns.patch.
+template <typename T, bool SILU, int NS, bool SHARE>
+__device__ __forceinline__ void gn_apply_down_body(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb, int H, int W, int G, const double* __restrict__ stats,
+          const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* __restrict__ out_act, T* __restrict__ out_raw,
+          int ncg, int nstrips, int nt_stores, const int by, const int bx) {
+    using Lane = GnLane<T, NS>;
+    constexpr int PER16 = Lane::PER16;
+    constexpr int LC = 2 * Lane::COLS + 2;          // local input columns 0 .. LC - 1 = taps 2 col + j (0 and LC - 1: the edge threads' own)
+    // [exchange buffer][row of the pair][local input column][slot]: activated, in T.  Named by the SHARE instantiation only: the barrier-free
+    // kernel has no such array
+    __shared__ uint4 xact[2][2][LC][NS];
+    const Lane ln(xa, Ca, xb, Cb, H, W, G, stats, gamma, beta, eps, ncg, nstrips, by);
+    const int C = Ca + Cb, slot = ln.slot, col = ln.col;
+    const int OH = H / 2, OW = W / 2;
+    const int ox = bx * Lane::COLS + col;
+    // (SHARE: a slot past a ragged last channel group loads nothing and a column past the image may still own input columns a live neighbour
+    //  filters - but every thread takes part in the barriers)
+    const bool live = ln.chan && ox < OW;
+    if (!SHARE && !live) return;
+    const long long obase = (long long)ln.b * OH * OW;
+    const int ix0 = 2 * ox - 1;
+    bool x_in[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x_in[j] = ln.chan && ix0 + j >= 0 && ix0 + j < W;
+    if (!SHARE) x_in[1] = true;                     // (ix0 + 1 = 2 ox < W for every live column: an unconditional load)
+    const bool first = col == 0, last = col == Lane::COLS - 1;
+    auto activate = [&](const uint4 qv, bool ok) -> uint4 { return gn_activate<T, SILU>(qv, ok, ln.pa, ln.pb); };
+    int buf = 0;
+
+    // raw taps of input row iy (zeros outside the image); false: the row is outside (uniform in the workgroup)
+    auto load_row = [&](int iy, uint4 (&q)[4]) -> bool {
         const bool rowok = iy >= 0 && iy < H;
-        const T* const row = src + (ibase + (long long)(rowok ? iy : 0) * W) * cs;
+        const T* const row = ln.src + (ln.ibase + (long long)(rowok ? iy : 0) * W) * ln.cs;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            q[j] = rowok && x_in[j] ? *reinterpret_cast<const uint4*>(row + (long long)(ix0 + j) * cs) : make_uint4(0u, 0u, 0u, 0u);
+            q[j] = rowok && x_in[j] ? *reinterpret_cast<const uint4*>(row + (long long)(ix0 + j) * ln.cs) : make_uint4(0u, 0u, 0u, 0u);
+        return rowok;
     };
-    // own activations of a row: the centre taps (to LDS for the neighbours) and, in the first / last column, the outer tap
-    auto own_acts = [&](int iy, const uint4 (&q)[4], uint4 (&a)[4], int buf, int r) {
-        const bool rowok = iy >= 0 && iy < H;       // (uniform in the workgroup)
+    // SHARE - own activations of a row: the centre taps (to LDS for the neighbours) and, in the first / last column, the outer tap
+    auto own_acts = [&](bool rowok, const uint4 (&q)[4], uint4 (&a)[4], int r) {
         a[0] = a[1] = a[2] = a[3] = make_uint4(0u, 0u, 0u, 0u);
         if (!rowok) return;
         a[1] = activate(q[1], x_in[1]);
@@ -527,70 +474,48 @@ __device__ __forceinline__ void gn_apply_down_share_body(const T* __restrict__ x
             if (first && last) a[3] = activate(q[3], x_in[3]);       // (one column per workgroup: never with NS <= 32, kept for completeness)
         }
     };
-    // the neighbours' activations of the outer taps (after the barrier)
-    auto nb_acts = [&](int iy, uint4 (&a)[4], int buf, int r) {
-        if (iy < 0 || iy >= H) return;
+    // SHARE - the neighbours' activations of the outer taps (after the barrier)
+    auto nb_acts = [&](bool rowok, uint4 (&a)[4], int r) {
+        if (!rowok) return;
         if (!first) a[0] = xact[buf][r][2 * col][slot];
         if (!last) a[3] = xact[buf][r][2 * col + 3][slot];
     };
-    // horizontal filter of one row: activated (hA) and raw (hR), taps in the order 0 .. 3
-    auto hfilter = [&](const uint4 (&a)[4], const uint4 (&q)[4], float (&hA)[PER16], float (&hR)[PER16]) {
+    // the horizontally filtered input rows iy (h0) and iy + 1 (h1), activated and raw
+    auto hrows = [&](int iy, float (&h0A)[PER16], float (&h0R)[PER16], float (&h1A)[PER16], float (&h1R)[PER16]) {
+        uint4 q0[4], q1[4];
+        if constexpr (SHARE) {
+            uint4 a0[4], a1[4];
+            buf ^= 1;
+            const bool ok0 = load_row(iy, q0), ok1 = load_row(iy + 1, q1);
+            own_acts(ok0, q0, a0, 0);
+            own_acts(ok1, q1, a1, 1);
+            __syncthreads();
+            nb_acts(ok0, a0, 0);
+            nb_acts(ok1, a1, 1);
+            gn_hfilter4<T>([&](int j) { return a0[j]; }, q0, h0A, h0R);
+            gn_hfilter4<T>([&](int j) { return a1[j]; }, q1, h1A, h1R);
+        } else {                                    // a row at a time, a tap activated where it is filtered
+            auto hrow = [&](int y, uint4 (&q)[4], float (&hA)[PER16], float (&hR)[PER16]) {
+                if (load_row(y, q)) { gn_hfilter4<T>([&](int j) { return activate(q[j], x_in[j]); }, q, hA, hR); return; }
 #pragma unroll
-        for (int e = 0; e < PER16; ++e) { hA[e] = 0.f; hR[e] = 0.f; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float wgt = (j == 0 || j == 3) ? 0.125f : 0.375f;
-            if constexpr (sizeof(T) == 2) {
-                uint32_t wl = tap_weight_bits(wgt, (T*)nullptr), wh = wl << 16;
-                keep_rw(wl); keep_rw(wh);            // (packed 16-bit operands of v_dot2c must come from registers)
-                const uint32_t aw[4] = {a[j].x, a[j].y, a[j].z, a[j].w}, rw[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    hA[2 * i] = dot2_acc(aw[i], wl, hA[2 * i], (T*)nullptr); hA[2 * i + 1] = dot2_acc(aw[i], wh, hA[2 * i + 1], (T*)nullptr);
-                    hR[2 * i] = dot2_acc(rw[i], wl, hR[2 * i], (T*)nullptr); hR[2 * i + 1] = dot2_acc(rw[i], wh, hR[2 * i + 1], (T*)nullptr);
-                }
-            } else {
-                alignas(16) T ya[PER16];
-                alignas(16) T xr[PER16];
-                *reinterpret_cast<uint4*>(ya) = a[j];
-                *reinterpret_cast<uint4*>(xr) = q[j];
-#pragma unroll
-                for (int e = 0; e < PER16; ++e) { hA[e] = fmaf(wgt, to_f32(ya[e]), hA[e]); hR[e] = fmaf(wgt, to_f32(xr[e]), hR[e]); }
-            }
+                for (int e = 0; e < PER16; ++e) { hA[e] = 0.f; hR[e] = 0.f; }
+            };
+            hrow(iy, q0, h0A, h0R);
+            hrow(iy + 1, q1, h1A, h1R);
         }
     };
     const int dn_rows = (OH + nstrips - 1) / nstrips;
-    const int oy0 = strip * dn_rows, oy1 = min(OH, oy0 + dn_rows);
+    const int oy0 = ln.strip * dn_rows, oy1 = min(OH, oy0 + dn_rows);
     float cA[PER16], cR[PER16];                     // carry: k0 h[2 oy - 1] + k1 h[2 oy]
-    int buf = 1;
     {
-        uint4 q0[4], q1[4], a0[4], a1[4];
-        load_row(2 * oy0 - 1, q0);
-        load_row(2 * oy0, q1);
-        own_acts(2 * oy0 - 1, q0, a0, buf, 0);
-        own_acts(2 * oy0, q1, a1, buf, 1);
-        __syncthreads();
-        nb_acts(2 * oy0 - 1, a0, buf, 0);
-        nb_acts(2 * oy0, a1, buf, 1);
         float h0A[PER16], h0R[PER16], h1A[PER16], h1R[PER16];
-        hfilter(a0, q0, h0A, h0R);
-        hfilter(a1, q1, h1A, h1R);
+        hrows(2 * oy0 - 1, h0A, h0R, h1A, h1R);
 #pragma unroll
         for (int e = 0; e < PER16; ++e) { cA[e] = fmaf(0.375f, h1A[e], 0.125f * h0A[e]); cR[e] = fmaf(0.375f, h1R[e], 0.125f * h0R[e]); }
     }
     for (int oy = oy0; oy < oy1; ++oy) {
-        buf ^= 1;
-        uint4 q2[4], q3[4], a2[4], a3[4];
-        load_row(2 * oy + 1, q2);
-        load_row(2 * oy + 2, q3);
-        own_acts(2 * oy + 1, q2, a2, buf, 0);
-        own_acts(2 * oy + 2, q3, a3, buf, 1);
-        __syncthreads();
-        nb_acts(2 * oy + 1, a2, buf, 0);
-        nb_acts(2 * oy + 2, a3, buf, 1);
         float h2A[PER16], h2R[PER16], h3A[PER16], h3R[PER16];
-        hfilter(a2, q2, h2A, h2R);
-        hfilter(a3, q3, h3A, h3R);
+        hrows(2 * oy + 1, h2A, h2R, h3A, h3R);
         float va[PER16], vr[PER16];
 #pragma unroll
         for (int e = 0; e < PER16; ++e) {
@@ -599,43 +524,37 @@ __device__ __forceinline__ void gn_apply_down_share_body(const T* __restrict__ x
             cA[e] = fmaf(0.375f, h3A[e], 0.125f * h2A[e]);
             cR[e] = fmaf(0.375f, h3R[e], 0.125f * h2R[e]);
         }
-        if (!live) continue;
-        const long long o = (obase + (long long)oy * OW + ox) * C + c;
-        if constexpr (sizeof(T) == 2) {
-            const uint4 qa = make_uint4(pack2(va[0], va[1], (T*)nullptr), pack2(va[2], va[3], (T*)nullptr),
-                                        pack2(va[4], va[5], (T*)nullptr), pack2(va[6], va[7], (T*)nullptr));
-            const uint4 qr = make_uint4(pack2(vr[0], vr[1], (T*)nullptr), pack2(vr[2], vr[3], (T*)nullptr),
-                                        pack2(vr[4], vr[5], (T*)nullptr), pack2(vr[6], vr[7], (T*)nullptr));
-            if (nt_stores) { store16_nt(out_act + o, qa); if (out_raw) store16_nt(out_raw + o, qr); }
-            else { *reinterpret_cast<uint4*>(out_act + o) = qa; if (out_raw) *reinterpret_cast<uint4*>(out_raw + o) = qr; }
-        } else {
-            alignas(16) T oa[PER16];
-            alignas(16) T orr[PER16];
-#pragma unroll
-            for (int e = 0; e < PER16; ++e) { from_f32(oa[e], va[e]); from_f32(orr[e], vr[e]); }
-            *reinterpret_cast<uint4*>(out_act + o) = *reinterpret_cast<const uint4*>(oa);
-            if (out_raw) *reinterpret_cast<uint4*>(out_raw + o) = *reinterpret_cast<const uint4*>(orr);
-        }
+        if (SHARE && !live) continue;
+        const long long o = (obase + (long long)oy * OW + ox) * C + ln.c;
+        gn_put(out_act + o, gn_pack<T>(va), nt_stores);
+        if (out_raw) gn_put(out_raw + o, gn_pack<T>(vr), nt_stores);
     }
+}
+template <typename T, bool SILU, int NS>
+__global__ __launch_bounds__(256)
+void gn_apply_down_kernel(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb, int H, int W, int G, const double* __restrict__ stats,
+          const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* __restrict__ out_act, T* __restrict__ out_raw,
+          int ncg, int nstrips, int nt_stores) {
+    gn_apply_down_body<T, SILU, NS, false>(xa, Ca, xb, Cb, H, W, G, stats, gamma, beta, eps, out_act, out_raw, ncg, nstrips, nt_stores, blockIdx.y, blockIdx.x);
+}
+template <typename T, bool SILU, int NS>
+__global__ __launch_bounds__(256)
+void gn_apply_down_group_kernel(const GnApplyProblem* __restrict__ tab, const GnFinItem* __restrict__ items, int Ca, int Cb, int G,
+           const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int nt_stores) {
+    gn_apply_group_item<T>(tab, items, Ca, Cb, G, gamma, beta, eps, nt_stores, [](auto... a) { gn_apply_down_body<T, SILU, NS, false>(a...); });
 }
 template <typename T, bool SILU, int NS>
 __global__ __launch_bounds__(256)
 void gn_apply_down_share_kernel(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb, int H, int W, int G, const double* __restrict__ stats,
           const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* __restrict__ out_act, T* __restrict__ out_raw,
           int ncg, int nstrips, int nt_stores) {
-    gn_apply_down_share_body<T, SILU, NS>(xa, Ca, xb, Cb, H, W, G, stats, gamma, beta, eps, out_act, out_raw, ncg, nstrips, nt_stores, blockIdx.y, blockIdx.x);
+    gn_apply_down_body<T, SILU, NS, true>(xa, Ca, xb, Cb, H, W, G, stats, gamma, beta, eps, out_act, out_raw, ncg, nstrips, nt_stores, blockIdx.y, blockIdx.x);
 }
-// the strips of SEVERAL problems in one launch (grouped evaluation of a ragged stream's micro-batches, common.h): blockIdx.y = an item
-// (problem, the y index of the problem's own launch) of a host-built list; a strip is computed by the code of its own launch
 template <typename T, bool SILU, int NS>
 __global__ __launch_bounds__(256)
 void gn_apply_down_share_group_kernel(const GnApplyProblem* __restrict__ tab, const GnFinItem* __restrict__ items, int Ca, int Cb, int G,
            const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int nt_stores) {
-    const GnFinItem it = items[blockIdx.y];
-    const GnApplyProblem& q = tab[it.problem];
-    if ((int)blockIdx.x >= q.cols) return;
-    gn_apply_down_share_body<T, SILU, NS>(static_cast<const T*>(q.xa), Ca, static_cast<const T*>(q.xb), Cb, q.H, q.W, G, q.stats, gamma, beta, eps,
-                      static_cast<T*>(q.out_act), static_cast<T*>(q.out_raw), q.ncg, q.nstrips, nt_stores, it.b, blockIdx.x);
+    gn_apply_group_item<T>(tab, items, Ca, Cb, G, gamma, beta, eps, nt_stores, [](auto... a) { gn_apply_down_body<T, SILU, NS, true>(a...); });
 }
 
 // The same for x2 UP: out[2i] = 3/4 x[i] + 1/4 x[i - 1], out[2i + 1] = 3/4 x[i] + 1/4 x[i + 1] per axis (k = [1,3,3,1], gain 2 per
@@ -644,113 +563,40 @@ void gn_apply_down_share_group_kernel(const GnApplyProblem* __restrict__ tab, co
 // (2 ix, 2 ix + 1) of both tensors; every pair of consecutive filtered rows (h[i], h[i + 1]) emits the output rows 2 i + 1 and
 // 2 i + 2.  The kernel is bound by its stores (two tensors of four times the input size: 8 x 16 B per thread and input row):
 // 4.1 TB/s, exactly what the LDS-tiled predecessor reached - a write-dominated stream does not get the copy rate on this part.
-constexpr int UP_ROWS = 16;                         // input rows per strip
 template <typename T, bool SILU, int NS>
-__device__ __forceinline__ void gn_apply_up_body(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb,
-                        int H, int W, int G, const double* __restrict__ stats,
-                        const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                        T* __restrict__ out_act, T* __restrict__ out_raw, int ncg, int nstrips, int nt_stores, const int by, const int bx) {
-    constexpr int PER16 = Elem<T>::PER16;
-    constexpr int CG = NS * PER16;
-    constexpr int UP_COLS = 256 / NS;               // input columns per workgroup
-    __shared__ float gtab[2 * CG];
-    const int C = Ca + Cb, tid = threadIdx.x;
-    const int slot = tid % NS, col = tid / NS;
+__device__ __forceinline__ void gn_apply_up_body(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb, int H, int W, int G, const double* __restrict__ stats,
+          const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* __restrict__ out_act, T* __restrict__ out_raw,
+          int ncg, int nstrips, int nt_stores, const int by, const int bx) {
+    using Lane = GnLane<T, NS>;
+    constexpr int PER16 = Lane::PER16;
+    const Lane ln(xa, Ca, xb, Cb, H, W, G, stats, gamma, beta, eps, ncg, nstrips, by);
+    const int C = Ca + Cb;
     const int OH = 2 * H, OW = 2 * W;
-    int t = by;
-    const int cg = t % ncg; t /= ncg;
-    const int strip = t % nstrips, b = t / nstrips;
-    const int gs = C / G;
-    if (tid < CG) {
-        const int cc = cg * CG + tid;
-        float sc = 0.f, sh = 0.f;
-        if (cc < C) {
-            const double n = (double)gs * H * W;
-            const int g = cc / gs;
-            const double m = stats[((long long)b * G + g) * 2] / n;
-            double var = stats[((long long)b * G + g) * 2 + 1] / n - m * m;
-            if (var < 0.0) var = 0.0;
-            const float pm = (float)m;
-            sc = (float)(1.0 / sqrt(var + (double)eps)) * gamma[cc];
-            sh = beta[cc] - pm * sc;
-        }
-        gtab[2 * tid] = sc; gtab[2 * tid + 1] = sh;
-    }
-    __syncthreads();
-    const int c = cg * CG + slot * PER16;
-    const int ix = bx * UP_COLS + col;
-    if (c >= C || ix >= W) return;
-    float pa[PER16], pb[PER16];
-#pragma unroll
-    for (int e = 0; e < PER16; ++e) { pa[e] = gtab[2 * (slot * PER16 + e)]; pb[e] = gtab[2 * (slot * PER16 + e) + 1]; }
-    const T* const src = (c < Ca) ? xa + c : xb + (c - Ca);
-    const int cs = (c < Ca) ? Ca : Cb;
-    const long long ibase = (long long)b * H * W;
-    const long long obase = (long long)b * OH * OW;
+    const int ix = bx * Lane::COLS + ln.col;        // input column
+    if (!ln.chan || ix >= W) return;
+    const long long obase = (long long)ln.b * OH * OW;
     const bool x_in[3] = {ix > 0, true, ix + 1 < W};
     struct HRow { float eA[PER16], oA[PER16], eR[PER16], oR[PER16]; };    // columns 2 ix (even) / 2 ix + 1 (odd), activated / raw
     auto hrow = [&](int iy, HRow& h) {
 #pragma unroll
         for (int e = 0; e < PER16; ++e) { h.eA[e] = 0.f; h.oA[e] = 0.f; h.eR[e] = 0.f; h.oR[e] = 0.f; }
         if (iy < 0 || iy >= H) return;
-        const T* const row = src + (ibase + (long long)iy * W) * cs;
+        const T* const row = ln.src + (ln.ibase + (long long)iy * W) * ln.cs;
         uint4 q[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-            q[j] = x_in[j] ? *reinterpret_cast<const uint4*>(row + (long long)(ix - 1 + j) * cs) : make_uint4(0u, 0u, 0u, 0u);
+            q[j] = x_in[j] ? *reinterpret_cast<const uint4*>(row + (long long)(ix - 1 + j) * ln.cs) : make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             // weights of this tap in the even / odd output column: left (1/4, 0), centre (3/4, 3/4), right (0, 1/4)
             const float we = j == 0 ? 0.25f : (j == 1 ? 0.75f : 0.f), wo = j == 0 ? 0.f : (j == 1 ? 0.75f : 0.25f);
-            alignas(16) T raw[PER16];
-            *reinterpret_cast<uint4*>(raw) = q[j];
-            if constexpr (sizeof(T) == 2) {
-                uint32_t aw[4] = {0u, 0u, 0u, 0u};
-                if (x_in[j]) {
-#pragma unroll
-                    for (int e = 0; e < PER16; e += 2) {
-                        f32x2 y = __builtin_elementwise_fma(f32x2{to_f32(raw[e]), to_f32(raw[e + 1])}, f32x2{pa[e], pa[e + 1]}, f32x2{pb[e], pb[e + 1]});
-                        if (SILU) y = silu2(y);
-                        aw[e / 2] = pack2(y.x, y.y, (T*)nullptr);
-                    }
-                }
-                const uint32_t r[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
-                if (j != 2) {
-                    uint32_t wl = tap_weight_bits(we, (T*)nullptr), wh = wl << 16;
-                    keep_rw(wl); keep_rw(wh);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        h.eA[2 * i] = dot2_acc(aw[i], wl, h.eA[2 * i], (T*)nullptr); h.eA[2 * i + 1] = dot2_acc(aw[i], wh, h.eA[2 * i + 1], (T*)nullptr);
-                        h.eR[2 * i] = dot2_acc(r[i], wl, h.eR[2 * i], (T*)nullptr); h.eR[2 * i + 1] = dot2_acc(r[i], wh, h.eR[2 * i + 1], (T*)nullptr);
-                    }
-                }
-                if (j != 0) {
-                    uint32_t wl = tap_weight_bits(wo, (T*)nullptr), wh = wl << 16;
-                    keep_rw(wl); keep_rw(wh);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        h.oA[2 * i] = dot2_acc(aw[i], wl, h.oA[2 * i], (T*)nullptr); h.oA[2 * i + 1] = dot2_acc(aw[i], wh, h.oA[2 * i + 1], (T*)nullptr);
-                        h.oR[2 * i] = dot2_acc(r[i], wl, h.oR[2 * i], (T*)nullptr); h.oR[2 * i + 1] = dot2_acc(r[i], wh, h.oR[2 * i + 1], (T*)nullptr);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < PER16; ++e) {
-                    const float xr = to_f32(raw[e]);
-                    float y = 0.f;
-                    if (x_in[j]) {
-                        y = fmaf(xr, pa[e], pb[e]);
-                        if (SILU) y = silu_f(y);
-                        T ya; from_f32(ya, y); y = to_f32(ya);
-                    }
-                    if (j != 2) { h.eA[e] = fmaf(we, y, h.eA[e]); h.eR[e] = fmaf(we, xr, h.eR[e]); }
-                    if (j != 0) { h.oA[e] = fmaf(wo, y, h.oA[e]); h.oR[e] = fmaf(wo, xr, h.oR[e]); }
-                }
-            }
+            const uint4 a = gn_activate<T, SILU>(q[j], x_in[j], ln.pa, ln.pb);
+            if (j != 2) gn_tap<T>(we, a, q[j], h.eA, h.eR);
+            if (j != 0) gn_tap<T>(wo, a, q[j], h.oA, h.oR);
         }
     };
     auto store_row = [&](int oy, const HRow& a, float wa_, const HRow& bq, float wb_) {     // out[oy] = wa_ a + wb_ bq, both columns
-        const long long o0 = (obase + (long long)oy * OW + 2 * ix) * C + c;
+        const long long o0 = (obase + (long long)oy * OW + 2 * ix) * C + ln.c;
         float v[4][PER16];
 #pragma unroll
         for (int e = 0; e < PER16; ++e) {
@@ -760,21 +606,11 @@ __device__ __forceinline__ void gn_apply_up_body(const T* __restrict__ xa, int C
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             T* const dst = (k < 2 ? out_act : out_raw);
-            if (dst == nullptr) continue;
-            alignas(16) T ov[PER16];
-            if constexpr (sizeof(T) == 2) {
-                *reinterpret_cast<uint4*>(ov) = make_uint4(pack2(v[k][0], v[k][1], (T*)nullptr), pack2(v[k][2], v[k][3], (T*)nullptr),
-                                                           pack2(v[k][4], v[k][5], (T*)nullptr), pack2(v[k][6], v[k][7], (T*)nullptr));
-            } else {
-#pragma unroll
-                for (int e = 0; e < PER16; ++e) from_f32(ov[e], v[k][e]);
-            }
-            if (nt_stores) store16_nt(dst + o0 + (k & 1) * C, *reinterpret_cast<const uint4*>(ov));
-            else *reinterpret_cast<uint4*>(dst + o0 + (k & 1) * C) = *reinterpret_cast<const uint4*>(ov);
+            if (dst != nullptr) gn_put(dst + o0 + (k & 1) * C, gn_pack<T>(v[k]), nt_stores);
         }
     };
     const int up_rows = (H + nstrips - 1) / nstrips;
-    const int iy0 = strip * up_rows, iy1 = min(H, iy0 + up_rows);
+    const int iy0 = ln.strip * up_rows, iy1 = min(H, iy0 + up_rows);
     HRow h0, h1;
     hrow(iy0 - 1, h0);
     for (int i = iy0 - 1; i < iy1; ++i) {            // the pair (h[i], h[i + 1]) emits the output rows 2 i + 1 and 2 i + 2
@@ -791,17 +627,11 @@ void gn_apply_up_kernel(const T* __restrict__ xa, int Ca, const T* __restrict__ 
           int ncg, int nstrips, int nt_stores) {
     gn_apply_up_body<T, SILU, NS>(xa, Ca, xb, Cb, H, W, G, stats, gamma, beta, eps, out_act, out_raw, ncg, nstrips, nt_stores, blockIdx.y, blockIdx.x);
 }
-// the strips of SEVERAL problems in one launch (grouped evaluation of a ragged stream's micro-batches, common.h): blockIdx.y = an item
-// (problem, the y index of the problem's own launch) of a host-built list; a strip is computed by the code of its own launch
 template <typename T, bool SILU, int NS>
 __global__ __launch_bounds__(256)
 void gn_apply_up_group_kernel(const GnApplyProblem* __restrict__ tab, const GnFinItem* __restrict__ items, int Ca, int Cb, int G,
            const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int nt_stores) {
-    const GnFinItem it = items[blockIdx.y];
-    const GnApplyProblem& q = tab[it.problem];
-    if ((int)blockIdx.x >= q.cols) return;
-    gn_apply_up_body<T, SILU, NS>(static_cast<const T*>(q.xa), Ca, static_cast<const T*>(q.xb), Cb, q.H, q.W, G, q.stats, gamma, beta, eps,
-                      static_cast<T*>(q.out_act), static_cast<T*>(q.out_raw), q.ncg, q.nstrips, nt_stores, it.b, blockIdx.x);
+    gn_apply_group_item<T>(tab, items, Ca, Cb, G, gamma, beta, eps, nt_stores, [](auto... a) { gn_apply_up_body<T, SILU, NS>(a...); });
 }
 
 // ---- the non-FIR members (fir=False) -----------------------------------------------------------------------------------------------
@@ -812,91 +642,61 @@ void gn_apply_up_group_kernel(const GnApplyProblem* __restrict__ tab, const GnFi
 //           block of both tensors).  The raw tensor is a copy of the loaded bits; the activated one is rounded once.
 //   MODE 4, 2 x 2 mean down: column = OUTPUT column; per output row four loads; the mean of the four (activated) values is taken in fp32,
 //           ((x00 + x01) + (x10 + x11)) / 4, and rounded once; two stores.
-// No value is shared between rows, so there is no carry and no LDS beyond the per-channel (scale, shift) table.
-constexpr int NV_ROWS = 16;                         // rows per strip (input rows up, output rows down)
+// No value is shared between rows, so there is no carry and no LDS beyond the per-channel (scale, shift) table.  The activations stay
+// unrounded fp32 until the one rounding of the output (fmaf + silu_f in every type: not gn_activate's values).
 template <typename T, bool SILU, int NS, int MODE>
 __global__ __launch_bounds__(256)
 void gn_apply_naive_kernel(const T* __restrict__ xa, int Ca, const T* __restrict__ xb, int Cb, int H, int W, int G, const double* __restrict__ stats,
           const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* __restrict__ out_act, T* __restrict__ out_raw,
           int ncg, int nstrips, int nt_stores) {
-    constexpr int PER16 = Elem<T>::PER16;
-    constexpr int CG = NS * PER16;
-    constexpr int COLS = 256 / NS;                  // columns per workgroup
-    __shared__ float gtab[2 * CG];
-    const int C = Ca + Cb, tid = threadIdx.x;
-    const int slot = tid % NS, col = tid / NS;
-    int t = blockIdx.y;                             // (channel group, strip, batch item)
-    const int cg = t % ncg; t /= ncg;
-    const int strip = t % nstrips, b = t / nstrips;
-    const int gs = C / G;
-    if (tid < CG) {                                 // (scale, shift) of this workgroup's channels: y = x * sc + sh
-        const int cc = cg * CG + tid;
-        float sc = 0.f, sh = 0.f;
-        if (cc < C) {
-            const double n = (double)gs * H * W;
-            const int g = cc / gs;
-            const double m = stats[((long long)b * G + g) * 2] / n;
-            double var = stats[((long long)b * G + g) * 2 + 1] / n - m * m;
-            if (var < 0.0) var = 0.0;
-            const float pm = (float)m;
-            sc = (float)(1.0 / sqrt(var + (double)eps)) * gamma[cc];
-            sh = beta[cc] - pm * sc;
-        }
-        gtab[2 * tid] = sc; gtab[2 * tid + 1] = sh;
-    }
-    __syncthreads();
+    using Lane = GnLane<T, NS>;
+    constexpr int PER16 = Lane::PER16;
+    const Lane ln(xa, Ca, xb, Cb, H, W, G, stats, gamma, beta, eps, ncg, nstrips, blockIdx.y);
+    const int C = Ca + Cb;
     const int LH = MODE == 3 ? H : H / 2, LW = MODE == 3 ? W : W / 2;     // the image the threads walk
     const int OH = MODE == 3 ? 2 * H : H / 2, OW = MODE == 3 ? 2 * W : W / 2;
-    const int c = cg * CG + slot * PER16;
-    const int lx = blockIdx.x * COLS + col;
-    if (c >= C || lx >= LW) return;
-    float pa[PER16], pb[PER16];
-#pragma unroll
-    for (int e = 0; e < PER16; ++e) { pa[e] = gtab[2 * (slot * PER16 + e)]; pb[e] = gtab[2 * (slot * PER16 + e) + 1]; }
-    const T* const src = (c < Ca) ? xa + c : xb + (c - Ca);
-    const int cs = (c < Ca) ? Ca : Cb;
-    const long long ibase = (long long)b * H * W;
-    const long long obase = (long long)b * OH * OW;
+    const int lx = blockIdx.x * Lane::COLS + ln.col;
+    if (!ln.chan || lx >= LW) return;
+    const long long obase = (long long)ln.b * OH * OW;
     auto decode = [&](const uint4& q, float (&r)[PER16], float (&y)[PER16]) {      // the raw values and SiLU(GN(.)) of one slot, fp32
         alignas(16) T raw[PER16];
         *reinterpret_cast<uint4*>(raw) = q;
 #pragma unroll
         for (int e = 0; e < PER16; ++e) {
             r[e] = to_f32(raw[e]);
-            y[e] = fmaf(r[e], pa[e], pb[e]);
+            y[e] = fmaf(r[e], ln.pa[e], ln.pb[e]);
             if (SILU) y[e] = silu_f(y[e]);
         }
     };
+    // (from_f32 in every type, where gn_pack rounds 16-bit pairs with pack2: the same values, but that instruction sequence costs the
+    //  <bf16_t, false, NS, 4> instantiations a wave of occupancy - 88 registers for 80)
     auto encode = [&](const float (&v)[PER16]) -> uint4 {
         alignas(16) T ov[PER16];
 #pragma unroll
         for (int e = 0; e < PER16; ++e) from_f32(ov[e], v[e]);
         return *reinterpret_cast<const uint4*>(ov);
     };
-    auto put = [&](T* dst, const uint4& q) {
-        if (nt_stores) store16_nt(dst, q);
-        else *reinterpret_cast<uint4*>(dst) = q;
-    };
+    auto put = [&](T* dst, const uint4& q) { gn_put(dst, q, nt_stores); };
     const int rows = (LH + nstrips - 1) / nstrips;
-    const int y0 = strip * rows, y1 = min(LH, y0 + rows);
+    const int y0 = ln.strip * rows, y1 = min(LH, y0 + rows);
     if (MODE == 3) {
 #pragma unroll 2
         for (int iy = y0; iy < y1; ++iy) {
-            const uint4 q = *reinterpret_cast<const uint4*>(src + (ibase + (long long)iy * W + lx) * cs);
+            const uint4 q = *reinterpret_cast<const uint4*>(ln.src + (ln.ibase + (long long)iy * W + lx) * ln.cs);
             float r[PER16], y[PER16];
             decode(q, r, y);
+            const long long o0 = (obase + (long long)(2 * iy) * OW + 2 * lx) * C + ln.c, o1 = o0 + (long long)OW * C;
             const uint4 qa = encode(y);
-            const long long o0 = (obase + (long long)(2 * iy) * OW + 2 * lx) * C + c, o1 = o0 + (long long)OW * C;
             put(out_act + o0, qa); put(out_act + o0 + C, qa); put(out_act + o1, qa); put(out_act + o1 + C, qa);
             if (out_raw != nullptr) { put(out_raw + o0, q); put(out_raw + o0 + C, q); put(out_raw + o1, q); put(out_raw + o1 + C, q); }
         }
     } else {
 #pragma unroll 2
         for (int oy = y0; oy < y1; ++oy) {
-            const T* const row0 = src + (ibase + (long long)(2 * oy) * W + 2 * lx) * cs;
-            const T* const row1 = row0 + (long long)W * cs;
-            const uint4 q00 = *reinterpret_cast<const uint4*>(row0), q01 = *reinterpret_cast<const uint4*>(row0 + cs);
-            const uint4 q10 = *reinterpret_cast<const uint4*>(row1), q11 = *reinterpret_cast<const uint4*>(row1 + cs);
+            const T* const row0 = ln.src + (ln.ibase + (long long)(2 * oy) * W + 2 * lx) * ln.cs;
+            const T* const row1 = row0 + (long long)W * ln.cs;
+            const uint4 q00 = *reinterpret_cast<const uint4*>(row0), q01 = *reinterpret_cast<const uint4*>(row0 + ln.cs);
+            const uint4 q10 = *reinterpret_cast<const uint4*>(row1), q11 = *reinterpret_cast<const uint4*>(row1 + ln.cs);
             float r0[PER16], a0[PER16], r1[PER16], a1[PER16], r2[PER16], a2[PER16], r3[PER16], a3[PER16], va[PER16], vr[PER16];
             decode(q00, r0, a0); decode(q01, r1, a1); decode(q10, r2, a2); decode(q11, r3, a3);
 #pragma unroll
@@ -904,7 +704,7 @@ void gn_apply_naive_kernel(const T* __restrict__ xa, int Ca, const T* __restrict
                 va[e] = ((a0[e] + a1[e]) + (a2[e] + a3[e])) * 0.25f;
                 vr[e] = ((r0[e] + r1[e]) + (r2[e] + r3[e])) * 0.25f;
             }
-            const long long o = (obase + (long long)oy * OW + lx) * C + c;
+            const long long o = (obase + (long long)oy * OW + lx) * C + ln.c;
             put(out_act + o, encode(va));
             if (out_raw != nullptr) put(out_raw + o, encode(vr));
         }
@@ -961,94 +761,81 @@ static int gn_stats_t(const void* xa, int Ca, const void* xb, int Cb, int B, int
     return STORM_OK;
 }
 
-// Rows per strip of the two resampling kernels: 16 where that already gives every CU four workgroups (the bench batch: thousands), halved
-// down to 4 for small calls.  One utterance per call (the reference's own operating point, enhancement.py:66-72) at 16 rows is 128
-// workgroups for the level-0 down-sampling launch - one wave per SIMD on half the chip, a launch that lasts as long as ONE strip's chain
-// of row loads (41 us for 33 MB, profiles/r05a_b1_eager_rocprofv3_kernel_stats.csv); short strips re-read 3 halo rows per strip (4 rows:
-// 1.4 x the reads) and finish sooner.  A strip boundary does not change an output's arithmetic (each output row is the same four-tap
-// combination of the same filtered rows), so the choice is invisible in the results (test_groupnorm_fir_fused, STORM_GN_ROWS sweep).
-static int strip_rows(int rows_total, long long wgs_per_strip, int dflt) {
-    if (switches().gn_rows > 0) return switches().gn_rows;
-    int r = dflt;
-    while (r > 4 && wgs_per_strip * cdiv(rows_total, r) < 4LL * device_cus()) r >>= 1;
-    return r;
+// ---- the launch of the strip walkers (one problem: storm_gn_apply; several: the grouped evaluation of common.h) --------------------------------
+// slots of a pixel per workgroup: the widest of 32 / 16 / 8 that tiles the channel count (256 channels of 16-bit data: 32)
+static int gn_slots(int C, int esize) {
+    const int slots = C / (16 / esize);
+    return switches().gn_wide == 0 ? 8 : (slots % 32 == 0 ? 32 : slots % 16 == 0 ? 16 : 8);
 }
-
-// The launch of the down-sampling kernel: channel groups, strips, and which of the two kernels.  The activation shared through LDS
-// (gn_apply_down_share_kernel) for full launches - at least four workgroups per CU; the barrier-free kernel for small calls (a chain of
-// latencies, not of instructions: measured slower there, profiles/r05_probe_gn_down_share.txt).  STORM_GN_DOWN_SHARE: 0 = this rule, 1 = never,
-// 2 = always (A/B, tests)
-struct DownPlan { int ncg, nstrips; long long gy; bool share; };
-static DownPlan down_plan(int C, int B, int H, int W, int per16, int NSr) {
-    const int OH = H / 2, OW = W / 2;
-    DownPlan d;
-    d.ncg = cdiv(C, NSr * per16);
-    d.nstrips = cdiv(OH, strip_rows(OH, (long long)cdiv(OW, 256 / NSr) * d.ncg * B, DN_ROWS));
-    d.gy = (long long)d.ncg * d.nstrips * B;
+// Channel groups, rows per strip and - down-sampling - which of the two kernels, for the P problems of one launch.
+// Rows per strip: 16 where that already gives every CU four workgroups (the bench batch: thousands), halved down to 4 for small calls.
+// One utterance per call (the reference's own operating point, enhancement.py:66-72) at 16 rows is 128 workgroups for the level-0
+// down-sampling launch - one wave per SIMD on half the chip, a launch that lasts as long as ONE strip's chain of row loads (41 us for
+// 33 MB, profiles/r05a_b1_eager_rocprofv3_kernel_stats.csv); short strips re-read 3 halo rows per strip (4 rows: 1.4 x the reads) and
+// finish sooner.  A strip boundary does not change an output's arithmetic (each output row is the same four-tap combination of the same
+// filtered rows), so the choice is invisible in the results (test_groupnorm_fir_fused, STORM_GN_ROWS sweep).
+// Down-sampling: the activation shared through LDS (gn_apply_down_share_kernel) for full launches - at least four workgroups per CU; the
+// barrier-free kernel for small calls (a chain of latencies, not of instructions: measured slower there,
+// profiles/r05_probe_gn_down_share.txt).  STORM_GN_DOWN_SHARE: 0 = this rule, 1 = never, 2 = always (A/B, tests)
+struct GnStrips { int NS, ncg, rows; bool share; };
+static GnStrips gn_strips(int resample, int C, int esize, int P, const int* B, const int* H, const int* W) {
+    GnStrips s;
+    s.NS = gn_slots(C, esize);
+    s.ncg = cdiv(C, s.NS * (16 / esize));
+    const bool down = resample == 2 || resample == 4;           // the image the threads walk: the output (down) / the input (up)
+    auto wgs = [&](int r) {
+        long long n = 0;
+        for (int g = 0; g < P; ++g) n += (long long)cdiv(down ? W[g] / 2 : W[g], 256 / s.NS) * s.ncg * B[g] * cdiv(down ? H[g] / 2 : H[g], r);
+        return n;
+    };
+    s.rows = GN_STRIP_ROWS;
+    if (switches().gn_rows > 0) s.rows = switches().gn_rows;
+    else while (s.rows > 4 && wgs(s.rows) < 4LL * device_cus()) s.rows >>= 1;
     const int shsw = switches().gn_down_share;
-    d.share = shsw == 2 || (shsw == 0 && (long long)cdiv(OW, 256 / NSr) * d.gy >= 4LL * device_cus());
-    return d;
+    s.share = resample == 2 && (shsw == 2 || (shsw == 0 && wgs(s.rows) >= 4LL * device_cus()));
+    return s;
+}
+static int gn_nt_stores(int resample) { return (resample & 1) ? (switches().gn_nt & 1) : ((switches().gn_nt >> 1) & 1); }   // STORM_GN_NT: bit 0 up, bit 1 down
+// f(NS as an integral-constant tag): the one place where the run-time slot count becomes a template argument
+template <typename F> static void gn_with_ns(int NS, F&& f) {
+    if (NS == 32) f(std::integral_constant<int, 32>{});
+    else if (NS == 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 8>{});
 }
 
-template <typename T, int R>
+template <typename T>
 static int gn_apply_t(const void* xa, int Ca, const void* xb, int Cb, int B, int H, int W, int G,
-                      const double* stats, const float* gamma, const float* beta, float eps, int silu,
+                      const double* stats, const float* gamma, const float* beta, float eps, int silu, int resample,
                       void* out_act, void* out_raw, hipStream_t st) {
-    const GnGeom g = gn_geom(Ca + Cb);
-    // slots of a pixel per workgroup: the widest of 32 / 16 / 8 that tiles the channel count (256 channels of 16-bit data: 32)
-    const int slots = (Ca + Cb) / Elem<T>::PER16;
-    const int NSr = switches().gn_wide == 0 ? 8 : (slots % 32 == 0 ? 32 : slots % 16 == 0 ? 16 : 8);
-    if (R == 2) {
-        const int OH = H / 2, OW = W / 2;
-        const DownPlan dp = down_plan(Ca + Cb, B, H, W, Elem<T>::PER16, NSr);
-        const int ncg = dp.ncg, nstrips = dp.nstrips;
-        const long long gy = dp.gy;
-        STORM_CHECK(OH > 0 && OW > 0 && gy < 65536, "storm_gn_apply: down-sampling grid %lld out of range", gy);
-        const bool share = dp.share;
-#define STORM_GN_DOWN1(KERN_, SILU_, NS_) hipLaunchKernelGGL((KERN_<T, SILU_, NS_>), dim3(cdiv(OW, 256 / NS_), (unsigned)gy), dim3(256), 0, st, \
-                           (const T*)xa, Ca, (const T*)xb, Cb, H, W, G, stats, gamma, beta, eps, (T*)out_act, (T*)out_raw, ncg, nstrips, (switches().gn_nt >> 1) & 1)
-#define STORM_GN_DOWN(SILU_, NS_) do { if (share) STORM_GN_DOWN1(gn_apply_down_share_kernel, SILU_, NS_); else STORM_GN_DOWN1(gn_apply_down_kernel, SILU_, NS_); } while (0)
-        if (silu) { if (NSr == 32) STORM_GN_DOWN(true, 32); else if (NSr == 16) STORM_GN_DOWN(true, 16); else STORM_GN_DOWN(true, 8); }
-        else { if (NSr == 32) STORM_GN_DOWN(false, 32); else if (NSr == 16) STORM_GN_DOWN(false, 16); else STORM_GN_DOWN(false, 8); }
-#undef STORM_GN_DOWN
-#undef STORM_GN_DOWN1
+    if (resample == 0) {
+        const GnGeom g = gn_geom(Ca + Cb);
+        const int OHW = H * W;
+        const int per_thread = pixels_per_thread((long long)B * OHW, g.PL, 32);
+        int ppb = g.PL * per_thread;
+        const int nblk = cdiv(OHW, ppb);
+        hipLaunchKernelGGL((gn_apply_kernel<T, 0>), dim3(nblk, B), dim3(g.NT), 0, st, (const T*)xa, Ca, (const T*)xb,
+                           Cb, H, W, G, stats, gamma, beta, eps, silu, (T*)out_act, (T*)out_raw, ppb, g.C8, g.PL);
         STORM_LAUNCH_CHECK();
         return STORM_OK;
     }
-    if (R == 1) {
-        const int ncg = cdiv(Ca + Cb, NSr * Elem<T>::PER16), nstrips = cdiv(H, strip_rows(H, (long long)cdiv(W, 256 / NSr) * ncg * B, UP_ROWS));
-        const long long gy = (long long)ncg * nstrips * B;
-        STORM_CHECK(gy < 65536, "storm_gn_apply: up-sampling grid %lld out of range", gy);
-#define STORM_GN_UP(SILU_, NS_) hipLaunchKernelGGL((gn_apply_up_kernel<T, SILU_, NS_>), dim3(cdiv(W, 256 / NS_), (unsigned)gy), dim3(256), 0, st, \
-                           (const T*)xa, Ca, (const T*)xb, Cb, H, W, G, stats, gamma, beta, eps, (T*)out_act, (T*)out_raw, ncg, nstrips, switches().gn_nt & 1)
-        if (silu) { if (NSr == 32) STORM_GN_UP(true, 32); else if (NSr == 16) STORM_GN_UP(true, 16); else STORM_GN_UP(true, 8); }
-        else { if (NSr == 32) STORM_GN_UP(false, 32); else if (NSr == 16) STORM_GN_UP(false, 16); else STORM_GN_UP(false, 8); }
-#undef STORM_GN_UP
-        STORM_LAUNCH_CHECK();
-        return STORM_OK;
-    }
-    if (R == 3 || R == 4) {                              // the non-FIR members: nearest x2 up / 2 x 2 mean down (gn_apply_naive_kernel)
-        const int LH = R == 3 ? H : H / 2, LW = R == 3 ? W : W / 2;
-        STORM_CHECK(LH > 0 && LW > 0, "storm_gn_apply: empty image");
-        const int ncg = cdiv(Ca + Cb, NSr * Elem<T>::PER16), nstrips = cdiv(LH, strip_rows(LH, (long long)cdiv(LW, 256 / NSr) * ncg * B, NV_ROWS));
-        const long long gy = (long long)ncg * nstrips * B;
-        STORM_CHECK(gy < 65536, "storm_gn_apply: resampling grid %lld out of range", gy);
-        constexpr int M = R == 3 ? 3 : 4;
-        const int nt = R == 3 ? (switches().gn_nt & 1) : ((switches().gn_nt >> 1) & 1);
-#define STORM_GN_NV(SILU_, NS_) hipLaunchKernelGGL((gn_apply_naive_kernel<T, SILU_, NS_, M>), dim3(cdiv(LW, 256 / NS_), (unsigned)gy), dim3(256), 0, st, \
-                           (const T*)xa, Ca, (const T*)xb, Cb, H, W, G, stats, gamma, beta, eps, (T*)out_act, (T*)out_raw, ncg, nstrips, nt)
-        if (silu) { if (NSr == 32) STORM_GN_NV(true, 32); else if (NSr == 16) STORM_GN_NV(true, 16); else STORM_GN_NV(true, 8); }
-        else { if (NSr == 32) STORM_GN_NV(false, 32); else if (NSr == 16) STORM_GN_NV(false, 16); else STORM_GN_NV(false, 8); }
-#undef STORM_GN_NV
-        STORM_LAUNCH_CHECK();
-        return STORM_OK;
-    }
-    const int OHW = H * W;
-    const int per_thread = pixels_per_thread((long long)B * OHW, g.PL, 32);
-    int ppb = g.PL * per_thread;
-    const int nblk = cdiv(OHW, ppb);
-    hipLaunchKernelGGL((gn_apply_kernel<T, 0>), dim3(nblk, B), dim3(g.NT), 0, st, (const T*)xa, Ca, (const T*)xb,
-                       Cb, H, W, G, stats, gamma, beta, eps, silu, (T*)out_act, (T*)out_raw, ppb, g.C8, g.PL);
+    const bool down = resample == 2 || resample == 4;
+    const int LH = down ? H / 2 : H, LW = down ? W / 2 : W;     // the image the threads walk
+    const GnStrips p = gn_strips(resample, Ca + Cb, (int)sizeof(T), 1, &B, &H, &W);
+    const int nstrips = cdiv(LH, p.rows);
+    const long long gy = (long long)p.ncg * nstrips * B;
+    STORM_CHECK(LH > 0 && LW > 0 && gy < 65536, "storm_gn_apply: resampling grid %lld out of range", gy);
+    gn_with_ns(p.NS, [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        auto launch = [&](auto act) {
+            constexpr bool SILU = decltype(act)::value;
+            const auto kern = resample == 1 ? gn_apply_up_kernel<T, SILU, NS>
+                            : resample == 2 ? (p.share ? gn_apply_down_share_kernel<T, SILU, NS> : gn_apply_down_kernel<T, SILU, NS>)
+                            : resample == 3 ? gn_apply_naive_kernel<T, SILU, NS, 3> : gn_apply_naive_kernel<T, SILU, NS, 4>;
+            hipLaunchKernelGGL(kern, dim3(cdiv(LW, 256 / NS), (unsigned)gy), dim3(256), 0, st, (const T*)xa, Ca, (const T*)xb, Cb, H, W, G, stats,
+                               gamma, beta, eps, (T*)out_act, (T*)out_raw, p.ncg, nstrips, gn_nt_stores(resample));
+        };
+        if (silu) launch(std::true_type{}); else launch(std::false_type{});
+    });
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }
@@ -1113,32 +900,22 @@ int fir_group_problem(int resample, const void* x, const void* add, void* out, i
     return resample == 1 ? fir_problem<1>(x, add, out, B, H, W, C, q) : fir_problem<2>(x, add, out, B, H, W, C, q);
 }
 // ---- grouped GroupNorm-apply + SiLU + FIR x2 (common.h) -----------------------------------------------------------------------------------
-static int gn_group_ns(int C, int dtype) {
-    const int per16 = dtype == STORM_F32 ? 4 : 8, slots = C / per16;
-    return switches().gn_wide == 0 ? 8 : (slots % 32 == 0 ? 32 : slots % 16 == 0 ? 16 : 8);
-}
 bool gn_apply_group_plan(int resample, int C, int P, const int* B, const int* H, const int* W, int dtype, GnApplyGroupPlan& plan) {
     if ((dtype != STORM_BF16 && dtype != STORM_F16) || (resample != 1 && resample != 2) || C % 8 != 0 || C > GN_MAX_C) return false;
-    const int NSr = gn_group_ns(C, dtype), ncg = cdiv(C, NSr * 8);
-    auto rows_of = [&](int g) { return resample == 1 ? H[g] : H[g] / 2; };
-    auto cols_of = [&](int g) { return cdiv(resample == 1 ? W[g] : W[g] / 2, 256 / NSr); };
-    auto wgs = [&](int r) { long long n = 0; for (int g = 0; g < P; ++g) n += (long long)cols_of(g) * ncg * B[g] * cdiv(rows_of(g), r); return n; };
-    int r = resample == 1 ? UP_ROWS : DN_ROWS;
-    if (switches().gn_rows > 0) r = switches().gn_rows;
-    else while (r > 4 && wgs(r) < 4LL * device_cus()) r >>= 1;      // strip_rows' rule on the GROUP's workgroups
-    plan.rows_per_strip = r;
-    const int shsw = switches().gn_down_share;
-    plan.share = resample == 2 && (shsw == 2 || (shsw == 0 && wgs(r) >= 4LL * device_cus()));
+    const GnStrips s = gn_strips(resample, C, 2, P, B, H, W);      // (16-bit only) the single launch's rule on the GROUP's workgroups
+    plan.rows_per_strip = s.rows;
+    plan.share = s.share;
     plan.max_cols = 0; plan.items = 0;
     for (int g = 0; g < P; ++g) {
-        if (rows_of(g) < 1 || (resample == 2 && (H[g] % 2 || W[g] % 2))) return false;
-        plan.max_cols = std::max(plan.max_cols, cols_of(g));
-        plan.items += (long long)ncg * cdiv(rows_of(g), r) * B[g];
+        const int rows = resample == 1 ? H[g] : H[g] / 2, cols = cdiv(resample == 1 ? W[g] : W[g] / 2, 256 / s.NS);
+        if (rows < 1 || (resample == 2 && (H[g] % 2 || W[g] % 2))) return false;
+        plan.max_cols = std::max(plan.max_cols, cols);
+        plan.items += (long long)s.ncg * cdiv(rows, s.rows) * B[g];
     }
     return plan.items > 0 && plan.items < 65536;
 }
 long long gn_apply_group_problem(int resample, int C, int B, int dtype, const GnApplyGroupPlan& plan, int g, GnApplyProblem& q, GnFinItem* items) {
-    const int NSr = gn_group_ns(C, dtype);
+    const int NSr = gn_slots(C, 2);
     q.ncg = cdiv(C, NSr * 8);
     q.nstrips = cdiv(resample == 1 ? q.H : q.H / 2, plan.rows_per_strip);
     q.cols = cdiv(resample == 1 ? q.W : q.W / 2, 256 / NSr);
@@ -1146,22 +923,24 @@ long long gn_apply_group_problem(int resample, int C, int B, int dtype, const Gn
     for (long long y = 0; y < gy; ++y) { items[y].problem = g; items[y].b = (int)y; }
     return gy;
 }
+template <typename T>
+static void gn_apply_group_t(int resample, const GnApplyProblem* dev_tab, const GnFinItem* it, const GnApplyGroupPlan& plan, int Ca, int Cb, int G,
+                             const float* gamma, const float* beta, float eps, hipStream_t st) {
+    gn_with_ns(gn_slots(Ca + Cb, (int)sizeof(T)), [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        const auto kern = resample == 1 ? gn_apply_up_group_kernel<T, true, NS>
+                        : plan.share ? gn_apply_down_share_group_kernel<T, true, NS> : gn_apply_down_group_kernel<T, true, NS>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)plan.max_cols, (unsigned)plan.items), dim3(256), 0, st, dev_tab, it, Ca, Cb, G, gamma, beta, eps,
+                           gn_nt_stores(resample));
+    });
+}
 int launch_gn_apply_group(int resample, const GnApplyProblem* dev_tab, const void* dev_items, const GnApplyGroupPlan& plan, int Ca, int Cb, int G,
                           const float* gamma, const float* beta, float eps, int dtype, hipStream_t st) {
     STORM_CHECK(dev_tab && dev_items && gamma && beta && plan.items > 0 && plan.items < 65536 && plan.max_cols > 0, "storm_gn_apply (group): bad arguments");
-    const int NSr = gn_group_ns(Ca + Cb, dtype);
     const GnFinItem* it = static_cast<const GnFinItem*>(dev_items);
-    const int nt = resample == 1 ? (switches().gn_nt & 1) : ((switches().gn_nt >> 1) & 1);
-#define STORM_GAG1(KERN_, T_, NS_) hipLaunchKernelGGL((KERN_<T_, true, NS_>), dim3((unsigned)plan.max_cols, (unsigned)plan.items), dim3(256), 0, st, dev_tab, it, Ca, Cb, G, gamma, beta, eps, nt)
-#define STORM_GAG(KERN_, T_) do { if (NSr == 32) STORM_GAG1(KERN_, T_, 32); else if (NSr == 16) STORM_GAG1(KERN_, T_, 16); else STORM_GAG1(KERN_, T_, 8); } while (0)
-#define STORM_GAGT(T_) do { if (resample == 1) STORM_GAG(gn_apply_up_group_kernel, T_); else if (plan.share) STORM_GAG(gn_apply_down_share_group_kernel, T_); \
-                            else STORM_GAG(gn_apply_down_group_kernel, T_); } while (0)
-    if (dtype == STORM_BF16) STORM_GAGT(bf16_t);
-    else if (dtype == STORM_F16) STORM_GAGT(half_t);
+    if (dtype == STORM_BF16) gn_apply_group_t<bf16_t>(resample, dev_tab, it, plan, Ca, Cb, G, gamma, beta, eps, st);
+    else if (dtype == STORM_F16) gn_apply_group_t<half_t>(resample, dev_tab, it, plan, Ca, Cb, G, gamma, beta, eps, st);
     else STORM_CHECK(false, "storm_gn_apply (group): dtype %d", dtype);
-#undef STORM_GAGT
-#undef STORM_GAG
-#undef STORM_GAG1
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }
@@ -1242,18 +1021,9 @@ extern "C" int storm_gn_apply(const void* xa, int Ca, const void* xb, int Cb, in
     STORM_CHECK(resample >= 0 && resample <= 4, "storm_gn_apply: resample=%d", resample);
     STORM_CHECK((resample != 2 && resample != 4) || (H % 2 == 0 && W % 2 == 0), "storm_gn_apply: x2 down needs even H, W");
     hipStream_t st = (hipStream_t)s;
-#define STORM_GN_DISPATCH(T)                                                                                   \
-    switch (resample) {                                                                                        \
-        case 0: return gn_apply_t<T, 0>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, out_act, out_raw, st); \
-        case 1: return gn_apply_t<T, 1>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, out_act, out_raw, st); \
-        case 2: return gn_apply_t<T, 2>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, out_act, out_raw, st); \
-        case 3: return gn_apply_t<T, 3>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, out_act, out_raw, st); \
-        default: return gn_apply_t<T, 4>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, out_act, out_raw, st); \
-    }
-    if (dtype == STORM_BF16) { STORM_GN_DISPATCH(bf16_t) }
-    if (dtype == STORM_F16) { STORM_GN_DISPATCH(half_t) }
-    if (dtype == STORM_F32) { STORM_GN_DISPATCH(float) }
-#undef STORM_GN_DISPATCH
+    if (dtype == STORM_BF16) return gn_apply_t<bf16_t>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, resample, out_act, out_raw, st);
+    if (dtype == STORM_F16) return gn_apply_t<half_t>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, resample, out_act, out_raw, st);
+    if (dtype == STORM_F32) return gn_apply_t<float>(xa, Ca, xb, Cb, B, H, W, groups, stats, gamma, beta, eps, silu, resample, out_act, out_raw, st);
     STORM_CHECK(false, "storm_gn_apply: dtype %d", dtype);
 }
 
@@ -1261,13 +1031,10 @@ extern "C" int storm_gn_apply(const void* xa, int Ca, const void* xb, int Cb, in
 extern "C" const char* storm_gn_apply_kernel_name(int C, int B, int H, int W, int silu, int resample, int dtype) {
     static thread_local char name[160];
     const char* const tn = dtype == STORM_F32 ? "float" : dtype == STORM_F16 ? "storm::half_t" : "storm::bf16_t";
-    const int per16 = dtype == STORM_F32 ? 4 : 8;
     if (resample == 0) { snprintf(name, sizeof(name), "storm::gn_apply_kernel<%s, 0>", tn); return name; }
-    const int slots = C / per16;
-    const int NSr = switches().gn_wide == 0 ? 8 : (slots % 32 == 0 ? 32 : slots % 16 == 0 ? 16 : 8);
-    if (resample >= 3) { snprintf(name, sizeof(name), "storm::gn_apply_naive_kernel<%s, %s, %d, %d>", tn, silu ? "true" : "false", NSr, resample); return name; }
-    const bool share = resample == 2 && down_plan(C, B, H, W, per16, NSr).share;
-    snprintf(name, sizeof(name), "storm::gn_apply_%s_kernel<%s, %s, %d>", resample == 1 ? "up" : share ? "down_share" : "down", tn, silu ? "true" : "false", NSr);
+    const GnStrips p = gn_strips(resample, C, dtype == STORM_F32 ? 4 : 2, 1, &B, &H, &W);
+    if (resample >= 3) { snprintf(name, sizeof(name), "storm::gn_apply_naive_kernel<%s, %s, %d, %d>", tn, silu ? "true" : "false", p.NS, resample); return name; }
+    snprintf(name, sizeof(name), "storm::gn_apply_%s_kernel<%s, %s, %d>", resample == 1 ? "up" : p.share ? "down_share" : "down", tn, silu ? "true" : "false", p.NS);
     return name;
 }
 

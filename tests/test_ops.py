@@ -702,7 +702,7 @@ def test_groupnorm_fir_fused(dev, dtype, resample, shape, switch):
     switch("STORM_GN_WIDE", 0)
     act8, raw8 = ops.gn_apply(xa, st, gam.to(dev), bet.to(dev), resample=resample)
     assert torch.equal(act, act8) and torch.equal(raw, raw8)
-    for rows in (4, 8, 16):          # rows per strip (strip_rows picks 4 ... 16 by the size of the call): the same bits whatever the strips
+    for rows in (4, 8, 16):          # rows per strip (gn_strips picks 4 ... 16 by the size of the call): the same bits whatever the strips
         switch("STORM_GN_ROWS", rows)
         actr, rawr = ops.gn_apply(xa, st, gam.to(dev), bet.to(dev), resample=resample)
         assert torch.equal(act, actr) and torch.equal(raw, rawr)
@@ -718,6 +718,40 @@ def test_groupnorm_fir_fused(dev, dtype, resample, shape, switch):
             acts, raws = ops.gn_apply(xa, st, gam.to(dev), bet.to(dev), resample=resample)
             assert torch.equal(act, acts) and torch.equal(raw, raws), (share, "wide")
             switch("STORM_GN_WIDE", 0)
+
+
+@pytest.mark.parametrize("dtype", DTYPES + [torch.float16])
+@pytest.mark.parametrize("resample", [1, 2])
+@pytest.mark.parametrize("shape,Ca", [((2, 72, 20, 36), 24), ((2, 256, 10, 12), 128)])
+def test_groupnorm_fir_fused_two_inputs(dev, dtype, resample, shape, Ca, switch):
+    """The up blocks call these kernels on cat[h, skip] (xa, xb) without building it: the two-input call is the one-input call on the
+    concatenated tensor, bit for bit, with the statistics of the unsplit tensor.  First shape: the split (24 | 48) falls inside the first
+    channel group at every slot width; second (128 | 128): on a channel-group boundary with 8 and 16 slots of a pixel per workgroup and
+    inside the group with 32 (16-bit types).  Both slot widths, both down-sampling kernels; want_raw=False leaves the activated output
+    as it is; silu=False is FIR(GN(x))."""
+    from storm_amd import ops
+    g = torch.Generator().manual_seed(5)
+    B, C, H, W = shape
+    x = torch.randn(B, C, H, W, generator=g)
+    gam, bet = 1 + 0.1 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    gd, bd = gam.to(dev), bet.to(dev)
+    xc = nhwc(x).to(dtype).to(dev)
+    xa, xb = xc[..., :Ca].contiguous(), xc[..., Ca:].contiguous()
+    st = ops.gn_stats(xc)
+    for wide in (1, 0):
+        switch("STORM_GN_WIDE", wide)
+        for share in ((1, 2) if resample == 2 else (0,)):
+            switch("STORM_GN_DOWN_SHARE", share)
+            act, raw = ops.gn_apply(xc, st, gd, bd, resample=resample)
+            act2, raw2 = ops.gn_apply(xa, st, gd, bd, xb=xb, resample=resample)
+            assert torch.equal(act, act2) and torch.equal(raw, raw2), (wide, share)
+            act1, none = ops.gn_apply(xa, st, gd, bd, xb=xb, resample=resample, want_raw=False)
+            assert none is None and torch.equal(act, act1), (wide, share)
+    switch("STORM_GN_WIDE", 1)
+    switch("STORM_GN_DOWN_SHARE", 0)
+    lin, _ = ops.gn_apply(xa, st, gd, bd, xb=xb, silu=False, resample=resample)
+    fir = NR.fir_up2 if resample == 1 else NR.fir_down2
+    assert rel_l2(nchw(lin.float().cpu()), fir(NR.group_norm(q(x, dtype), gam, bet))) < tol(dtype, 2e-6, 5e-3)
 
 
 def test_fir_golden(dev, golden):
