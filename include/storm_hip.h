@@ -431,6 +431,44 @@ int storm_istft(const float* spec, const float* peak, float* wav, float* frames,
                 const int* row_len, storm_stream_t s);
 
 /* ------------------------------------------------------------------------------------------
+ * ConvTasNet (backbones/convtasnet.py): the time-domain denoiser.  Activations are channels-last [B][L][C] in `dtype`
+ * (C % 8 == 0); the TCN's running sums `output` / `skip_connection` are fp32 [B][L][BN]; statistics are fp32.  A global layer
+ * norm (GroupNorm(1, C, eps) over all of C x L of a row) is never materialised: the producing kernel writes per-wave
+ * (sum, sumsq) partials, storm_tasnet_gln_finalize turns them into stats[B][2] = (mean, rstd), the consumer applies
+ * (x - mean) * rstd * gamma_c + beta_c while it loads its operand.
+ * ------------------------------------------------------------------------------------------ */
+enum { STORM_TASNET_ENCODE = 0, STORM_TASNET_POINTWISE = 1, STORM_TASNET_DEPTHWISE = 2 };
+/* partial-sum slots per row that the kernel `op` (above) writes for L frames of C output channels: part = fp32 [B][slots][2] */
+int storm_tasnet_num_partials(int op, int L, int C);
+/* pad_signal (convtasnet.py:75-94) + Conv1d(1, N, win, stride = win / 2, bias=False): wav fp32 [B][T] (row stride wav_stride)
+ * -> enc [B][L][N], L = storm_tasnet_frames(T, win); wT = the weight transposed, fp32 [win][N]; part: the partials for TCN.LN. */
+int storm_tasnet_frames(long long T, int win);
+int storm_tasnet_encode(const float* wav, long long wav_stride, const float* wT, void* enc, float* part, int B, long long T,
+                        int N, int win, int dtype, storm_stream_t s);
+int storm_tasnet_gln_finalize(const float* part, float* stats, int B, int nparts, long long count, float eps, storm_stream_t s);
+/* 1x1 convolution as an MFMA GEMM: out[b][l][co] = sum_ci w[co][ci] * pre(x[b][l][ci]) + bias[co].
+ *   x: [B][L][Cin] in dtype, or fp32 when x_f32 (a running sum; rounded to dtype as it is loaded); w: [Cout][Cin] in dtype.
+ *   pre: norm_stats != NULL: the norm-apply with gamma / beta fp32 [Cin]; else prelu_in != NULL: PReLU with the scalar slope
+ *        *prelu_in; else none.
+ *   res_skip == 0: out [B][L][Cout] (fp32 when out_f32), after the scalar PReLU *prelu_out when given; part != NULL: partials
+ *        of the stored values for the next norm.
+ *   res_skip != 0: res_out and skip_out as ONE GEMM, w = cat[res_out.weight, skip_out.weight] ([Cout = 2 BN][Cin]): columns
+ *        [0, BN) are added to out = `output`, columns [BN, 2 BN) to skip = `skip_connection`, both fp32 [B][L][BN], in place. */
+int storm_tasnet_pointwise(const void* x, int x_f32, const void* w, const float* bias, void* out, int out_f32, float* skip,
+                           int res_skip, const float* norm_stats, const float* gamma, const float* beta, const float* prelu_in,
+                           const float* prelu_out, float* part, int B, int L, int Cin, int Cout, int dtype, storm_stream_t s);
+/* Conv1d(C, C, 3, dilation = padding = d, groups = C) on the norm-applied x, + bias, scalar PReLU, partials of the next norm.
+ * w3 = the weight transposed, fp32 [3][C].  The zero padding follows the norm: a tap outside [0, L) adds 0; d >= L leaves the
+ * centre tap. */
+int storm_tasnet_depthwise(const void* x, const float* w3, const float* bias, const float* norm_stats, const float* gamma,
+                           const float* beta, const float* prelu, void* out, float* part, int B, int L, int C, int dilation,
+                           int dtype, storm_stream_t s);
+/* sigmoid(mask) * enc, then ConvTranspose1d(N, 1, win, stride = win / 2, bias=False) as a gather (no atomics): mask, enc
+ * [B][L][N]; wd fp32 [N][win]; out fp32 [B][(L - 1) * stride + win] - the padded length, untrimmed as the reference returns it. */
+int storm_tasnet_decode(const void* mask, const void* enc, const float* wd, float* out, int B, int L, int N, int win, int dtype,
+                        storm_stream_t s);
+
+/* ------------------------------------------------------------------------------------------
  * Program interpreter: runs a whole NCSN++ forward (or any op list) with one host call.
  * The op list is planned on the host side (storm_amd/backbones/plan.py) once per
  * (model, B, F, T, dtype); pointers are offsets into the caller-owned buffers in `bufs`.

@@ -133,6 +133,13 @@ _SIGNATURES = {
     "storm_peak_abs": ([_vp, _vp, _i, _ll, _ll, _vp, _vp], C.c_int),
     "storm_stft": ([_vp, _vp, _vp, _vp, _vp, _i, _ll, _ll, _i, _i, _i, _i, _f, _f, _vp, _vp], C.c_int),
     "storm_istft": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _ll, _ll, _i, _i, _f, _f, _vp, _vp], C.c_int),
+    "storm_tasnet_num_partials": ([_i, _i, _i], C.c_int),
+    "storm_tasnet_frames": ([_ll, _i], C.c_int),
+    "storm_tasnet_encode": ([_vp, _ll, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp], C.c_int),
+    "storm_tasnet_gln_finalize": ([_vp, _vp, _i, _i, _ll, _f, _vp], C.c_int),
+    "storm_tasnet_pointwise": ([_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], C.c_int),
+    "storm_tasnet_depthwise": ([_vp] * 9 + [_i, _i, _i, _i, _i, _vp], C.c_int),
+    "storm_tasnet_decode": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], C.c_int),
     "storm_program_run": ([C.POINTER(Op), _i, C.POINTER(_vp), _i, _i, _vp], C.c_int),
     "storm_ncsnpp_num_tensors": ([C.POINTER(NcsnppConfig)], C.c_int),
     "storm_ncsnpp_tensor_info": ([C.POINTER(NcsnppConfig), _i, C.c_char_p, _i, C.POINTER(C.c_int), C.POINTER(C.c_longlong)], C.c_int),

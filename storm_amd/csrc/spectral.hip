@@ -5,6 +5,8 @@
 // products in fp32, sums in fp64.  Semantics are torch.stft / torch.istft with center=True,
 // reflect padding, periodic Hann, onesided output, window-envelope normalisation.
 #include "common.h"
+#define STORM_TASNET_IMPL          // the time-domain network's kernels (ConvTasNet) are compiled with the 1-D signal code
+#include "tasnet.h"
 
 namespace storm {
 

@@ -331,12 +331,15 @@ class ScoreModel(_Base):
 
 
 class DiscriminativeModel(ScoreModel):
-    """Predictive NCSN++ denoiser (model.py:320-370)."""
+    """Predictive denoiser (model.py:320-370): NCSN++ on the spectrogram, or a time-domain backbone (FORCE_STFT_OUT: ConvTasNet)
+    between an iSTFT and an STFT."""
 
     def _set_score_sign(self):
         pass
 
     def forward(self, y):
+        if getattr(self.dnn, "FORCE_STFT_OUT", False):        # a time-domain net (ConvTasNet): it is handed the waveform (model.py:323-324)
+            y = self._istft(self._backward_transform(y.squeeze(1)))
         t = torch.ones(y.shape[0], device=y.device)
         return self.dnn(y, t)
 
@@ -344,6 +347,8 @@ class DiscriminativeModel(ScoreModel):
         with torch.no_grad():
             Y, peak, T_orig = self._prepare(y)
             X_hat = self(Y)
+            if getattr(self.dnn, "FORCE_STFT_OUT", False):    # ... and its waveform goes back to a spectrogram (model.py:362-363)
+                X_hat = self._forward_transform(self._stft(X_hat)).unsqueeze(1)
             return self.data_module.spec_to_wav(X_hat, T_orig, peak).squeeze()
 
 

@@ -653,3 +653,88 @@ def istft(spec, length, peak=None, n_fft=510, hop=128, spec_factor=1.0, spec_abs
                                 length, wav.stride(0), n_fft, hop, float(spec_factor), float(spec_abs_exponent), L.ptr(rl),
                                 L.stream()), "storm_istft")
     return wav
+
+
+# ---------------------------------------------------------------- ConvTasNet --------------
+TASNET_ENCODE, TASNET_POINTWISE, TASNET_DEPTHWISE = 0, 1, 2
+
+
+def tasnet_frames(T, win):
+    """frames of a T-sample waveform after pad_signal (convtasnet.py:75-94) under Conv1d(win, stride = win // 2)"""
+    n = L.lib().storm_tasnet_frames(int(T), int(win))
+    if n <= 0:
+        raise L.StormError(f"storm_tasnet_frames({T}, {win}) failed")
+    return n
+
+
+def _tasnet_part(op, B, Lf, Cc, like):
+    n = L.lib().storm_tasnet_num_partials(op, Lf, Cc)
+    if n <= 0:
+        raise L.StormError(f"storm_tasnet_num_partials({op}, {Lf}, {Cc}) failed")
+    return _alloc((B, n, 2), torch.float32, like)
+
+
+def tasnet_encode(wav, wT, dtype):
+    """wav [B, T] fp32, wT [win, N] fp32 -> (enc [B, L, N] in dtype, partial sums of enc for TCN.LN)"""
+    B, T = wav.shape
+    win, N = wT.shape
+    Lf = tasnet_frames(T, win)
+    enc = _alloc((B, Lf, N), dtype, wav)
+    part = _tasnet_part(TASNET_ENCODE, B, Lf, N, wav)
+    L.check(L.lib().storm_tasnet_encode(L.ptr_rows(wav), wav.stride(0), L.ptr(wT), L.ptr(enc), L.ptr(part), B, T, N, win, L.dt(dtype),
+                                        L.stream()), "storm_tasnet_encode")
+    return enc, part
+
+
+def tasnet_gln_finalize(part, count, eps=1e-8):
+    """partials [B, n, 2] of a row's C x L values -> stats [B, 2] = (mean, rstd) of GroupNorm(1, C, eps)"""
+    B, n, _ = part.shape
+    stats = _alloc((B, 2), torch.float32, part)
+    L.check(L.lib().storm_tasnet_gln_finalize(L.ptr(part), L.ptr(stats), B, n, int(count), float(eps), L.stream()), "storm_tasnet_gln_finalize")
+    return stats
+
+
+def tasnet_pointwise(x, w, bias, dtype, norm=None, prelu_in=None, prelu_out=None, out_f32=False, partials=False, res_skip=None):
+    """1x1 convolution on the MFMA: x [B, L, Cin] (dtype, or fp32 = a running sum), w [Cout, Cin] in dtype, bias fp32.
+    norm = (stats, gamma, beta): norm-apply on load; prelu_in / prelu_out: 1-element slope tensors (PReLU on load / in the epilogue).
+    res_skip = (output, skip): the fused res_out + skip_out form - adds to both fp32 [B, L, Cout / 2] tensors in place, returns None.
+    Otherwise returns out [B, L, Cout] (and its partial sums with partials=True)."""
+    B, Lf, Cin = x.shape
+    Cout = w.shape[0]
+    if w.dtype != dtype or w.shape[1] != Cin or x.dtype not in (dtype, torch.float32):
+        raise L.StormError(f"tasnet_pointwise: x {tuple(x.shape)} {x.dtype}, w {tuple(w.shape)} {w.dtype}, compute dtype {dtype}")
+    stats, gamma, beta = norm if norm is not None else (None, None, None)
+    if res_skip is not None:
+        out, skip = res_skip
+        if not (out.dtype == skip.dtype == torch.float32 and tuple(out.shape) == tuple(skip.shape) == (B, Lf, Cout // 2)):
+            raise L.StormError("tasnet_pointwise: res_skip needs two fp32 [B, L, Cout / 2] tensors")
+        part = None
+    else:
+        out, skip = _alloc((B, Lf, Cout), torch.float32 if out_f32 else dtype, x), None
+        part = _tasnet_part(TASNET_POINTWISE, B, Lf, Cout, x) if partials else None
+    L.check(L.lib().storm_tasnet_pointwise(L.ptr(x), int(x.dtype == torch.float32), L.ptr(w), L.ptr(bias), L.ptr(out), int(out.dtype == torch.float32),
+                                           L.ptr(skip), int(res_skip is not None), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(prelu_in),
+                                           L.ptr(prelu_out), L.ptr(part), B, Lf, Cin, Cout, L.dt(dtype), L.stream()), "storm_tasnet_pointwise")
+    if res_skip is not None:
+        return None
+    return (out, part) if partials else out
+
+
+def tasnet_depthwise(x, w3, bias, norm, prelu, dilation):
+    """x [B, L, C] -> (PReLU(dconv(norm(x)) + bias) [B, L, C], its partial sums); w3 [3, C] fp32; norm = (stats, gamma, beta)"""
+    B, Lf, Cc = x.shape
+    stats, gamma, beta = norm
+    out = torch.empty_like(x)
+    part = _tasnet_part(TASNET_DEPTHWISE, B, Lf, Cc, x)
+    L.check(L.lib().storm_tasnet_depthwise(L.ptr(x), L.ptr(w3), L.ptr(bias), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(prelu), L.ptr(out),
+                                           L.ptr(part), B, Lf, Cc, int(dilation), L.dt(x), L.stream()), "storm_tasnet_depthwise")
+    return out, part
+
+
+def tasnet_decode(mask, enc, wd):
+    """sigmoid(mask) * enc [B, L, N] through ConvTranspose1d(N, 1, win, stride = win // 2): fp32 [B, (L - 1) * stride + win]; wd [N, win] fp32"""
+    B, Lf, N = enc.shape
+    win = wd.shape[1]
+    out = _alloc((B, (Lf - 1) * (win // 2) + win), torch.float32, enc)
+    L.check(L.lib().storm_tasnet_decode(L.ptr(mask), L.ptr(enc), L.ptr(wd), L.ptr(out), B, Lf, N, win, L.dt(enc), L.stream()), "storm_tasnet_decode")
+    return out
