@@ -362,6 +362,39 @@ int storm_sde_predictor_step_rows_rs(float* x, float* x_mean, const float* score
 /* out = a_b (y - x) - 1/2 g_b^2 score: the probability-flow right-hand side (sdes.py:92-145 with probability_flow=True) */
 int storm_sde_pf_drift_rows(float* out, const float* x, const float* y, const float* score, const float* a_rows,
                             const float* g_rows, int B, long long n, storm_stream_t s);
+/* ---- validation loss: the reference's `_step`, the number logged as valid_loss (model.py:138-154 ScoreModel, :329-349
+ * DiscriminativeModel, :560-595 StochasticRegenerationModel).  Rows as above: complex64 [B][n], one kernel per pass.
+ * Forward diffusion  xt[b] = mean_b(x0, y) + std_rows[b] z  (SDE.marginal_prob + model.py:144-150; sdes.py:210-231 OUVESDE,
+ * :296-306 OUVPSDE) without a `mean` tensor.  m_rows / std_rows: the mean factor and the std at t_b, device fp32 [B], formed by
+ * the caller with the reference's own fp32 expressions.  form 0: m x0 + (1 - m) y (OUVESDE._mean, 1 - m in fp32 in the kernel);
+ * form 1: y + m (x0 - y) (OUVPSDE._mean).  z NULL: drawn in the kernel from (seed, offset) as storm_sde_prior_rows does. */
+int storm_sde_perturb_rows(const float* x0, const float* y, const float* z, float* xt, const float* m_rows,
+                           const float* std_rows, int form, int B, long long n, uint64_t seed, uint64_t offset,
+                           storm_stream_t s);
+int storm_sde_perturb_rows_rs(const float* x0, const float* y, const float* z, float* xt, const float* m_rows,
+                              const float* std_rows, int form, int B, long long n, uint64_t seed, uint64_t offset,
+                              const uint64_t* row_seeds, storm_stream_t s);
+/* Denoising-score-matching residual per row, out[b] = 0.5 sum_i rho(score[b][i] std_rows[b] + z[b][i]), fp32 [B]: err formed in
+ * fp32 (model.py:151-152), rho = |.|^2 (kind 0, `mse`) or |.| (kind 1, `mae`) and the sum in fp64 (ScoreModel._loss model.py:113-122,
+ * loss_fn_score :468-470; the caller takes the mean or the sum of the rows).  z NULL: re-drawn in the kernel from the (seed, offset)
+ * / row_seeds the perturbation used - the noise never exists in memory.  row_frames (device int [B], may be NULL) with T = frames
+ * per row (n % T == 0): row b counts only the elements whose frame index i % T is below row_frames[b] (the zero frames of a ragged
+ * or padded batch stay out).  Per-block fp64 partials, then a fixed-order row sum; the block count depends on n only: a row's value
+ * is the same in every run and every batch.  scratch: caller-owned, >= storm_dsm_loss_scratch_bytes(B, n) bytes. */
+long long storm_dsm_loss_scratch_bytes(int B, long long n);
+int storm_dsm_loss_rows(const float* score, const float* z, float* out, void* scratch, long long scratch_bytes,
+                        const float* std_rows, const int* row_frames, int T, int kind, int B, long long n, uint64_t seed,
+                        uint64_t offset, storm_stream_t s);
+int storm_dsm_loss_rows_rs(const float* score, const float* z, float* out, void* scratch, long long scratch_bytes,
+                           const float* std_rows, const int* row_frames, int T, int kind, int B, long long n, uint64_t seed,
+                           uint64_t offset, const uint64_t* row_seeds, storm_stream_t s);
+/* The predictive models' losses per row (DiscriminativeModel._loss model.py:329-343, loss_fn_denoiser :479-481), out[b] fp32, the
+ * same reduction: kind 0  0.5 sum (a - b)^2 over the n FLOATS of a row (a complex spectrogram through its float view, or a real
+ * waveform); kind 1  0.5 sum |a - b| over n COMPLEX elements; kind 2  the same over n real samples.  row_frames / T as above for
+ * complex rows (kinds 0 and 1; kind 0: n even, T divides n / 2).  scratch >= storm_dsm_loss_scratch_bytes(B, n).  (`sisdr`,
+ * model.py:341-342, is storm_si_sdr with eps = 1e-10.) */
+int storm_pair_loss_rows(const float* a, const float* b, float* out, void* scratch, long long scratch_bytes,
+                         const int* row_frames, int T, int kind, int B, long long n, storm_stream_t s);
 /* ---- probability-flow ODE sampler (sampling/__init__.py:71-141 hands the state to scipy's RK45 on the host) ----
  * out = x + h * sum_{j<n_terms} coef[j] K[j]   (one Runge-Kutta stage; K = host array of device pointers, <= 7) */
 int storm_rk_combine(float* out, const float* x, const float* const* K, const float* coef, int n_terms, float h,

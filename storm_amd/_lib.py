@@ -122,6 +122,12 @@ _SIGNATURES = {
     "storm_sde_prior_rows_rs": ([_vp, _vp, _vp, _vp, _i, _ll, _u64, _u64, _vp, _vp], C.c_int),
     "storm_sde_predictor_step_rows_rs": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _u64, _u64, _vp, _vp], C.c_int),
     "storm_sde_pf_drift_rows": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _vp], C.c_int),
+    "storm_sde_perturb_rows": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _ll, _u64, _u64, _vp], C.c_int),
+    "storm_sde_perturb_rows_rs": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _ll, _u64, _u64, _vp, _vp], C.c_int),
+    "storm_dsm_loss_scratch_bytes": ([_i, _ll], C.c_longlong),
+    "storm_dsm_loss_rows": ([_vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _i, _i, _ll, _u64, _u64, _vp], C.c_int),
+    "storm_dsm_loss_rows_rs": ([_vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _i, _i, _ll, _u64, _u64, _vp, _vp], C.c_int),
+    "storm_pair_loss_rows": ([_vp, _vp, _vp, _vp, _ll, _vp, _i, _i, _i, _ll, _vp], C.c_int),
     "storm_rk_combine": ([_vp, _vp, C.POINTER(_vp), C.POINTER(C.c_float), _i, _f, _ll, _vp], C.c_int),
     "storm_rk_scaled_sumsq": ([_vp, _vp, _i, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_float), _i, _f, _f, _f, _ll, _vp], C.c_int),
     "storm_rk_combine_rows": ([_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _i, _ll, _vp], C.c_int),

@@ -396,7 +396,95 @@ __global__ void si_sdr_kernel(const float* __restrict__ s, const float* __restri
     }
 }
 
+// ---- validation loss: forward diffusion and the denoising-score-matching residual (model.py:138-154, 560-595) ----------------
+// x_t = mean_b(x0, y) + std_b z on the complex64 state in one pass, no `mean` tensor.  m_rows / std_rows: the mean factor and the
+// perturbation std at t_b, device fp32 [B], the SDE's own torch expressions (sdes.py:210-231, 296-306).  The mean in the two
+// operation orders of the reference: FORM 0 (OUVESDE._mean, sdes.py:210-213)  m x0 + (1 - m) y, 1 - m formed in fp32 here;
+// FORM 1 (OUVPSDE._mean, sdes.py:296-299)  y + m (x0 - y).
+template <int FORM, class Key>
+__global__ void perturb_kernel(const float* __restrict__ x0, const float* __restrict__ y, const float* __restrict__ z,
+                               float* __restrict__ xt, long long n, const float* __restrict__ m_rows,
+                               const float* __restrict__ std_rows, Key key, uint64_t offset) {
+    const int b = blockIdx.y;
+    const float m = m_rows[b], sd = std_rows[b];
+    const float om = 1.0f - m;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long k = (long long)b * n + i;
+        const float2 xx = reinterpret_cast<const float2*>(x0)[k];
+        const float2 yy = reinterpret_cast<const float2*>(y)[k];
+        const float2 zz = get_noise(z, b, i, k, key, offset);
+        float2 mean;
+        if (FORM == 0) mean = make_float2(m * xx.x + om * yy.x, m * xx.y + om * yy.y);
+        else mean = make_float2(yy.x + m * (xx.x - yy.x), yy.y + m * (xx.y - yy.y));
+        reinterpret_cast<float2*>(xt)[k] = make_float2(mean.x + sd * zz.x, mean.y + sd * zz.y);      // model.py:150
+    }
+}
+
+// One block's share of a row's loss sum -> part[b][block] (fp64); loss_rows_finish_kernel adds a row's shares in a fixed order.
+// The block count per row depends on the row length only and nothing is atomic, so a row's sum is the same number in every run and
+// in whatever batch the row sits (as rk_scaled_sumsq_rows_kernel).
+__device__ inline void loss_block_partial(double acc, double* __restrict__ part) {
+    __shared__ double red[4];
+    acc = wave_sum_d(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(long long)blockIdx.y * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+// err = score std_b + z in fp32 (model.py:152); rho = |err|^2 (kind 0, `mse`) or |err| (kind 1, `mae`) and the sum in fp64
+// (model.py:113-122, 468-470).  z is the injected tensor or the draw of (key, offset) - the one perturb_kernel made, never stored.
+// row_frames: row b counts the elements whose frame i % T lies below row_frames[b] (NULL: all).
+template <class Key>
+__global__ void dsm_loss_kernel(double* __restrict__ part, const float* __restrict__ score, const float* __restrict__ z,
+                                const float* __restrict__ std_rows, const int* __restrict__ row_frames, long long n, int T,
+                                int kind, Key key, uint64_t offset) {
+    const int b = blockIdx.y;
+    const float sd = std_rows[b];
+    const int frames = row_frames ? row_frames[b] : 0;
+    double acc = 0.0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        if (row_frames && (int)(i % T) >= frames) continue;
+        const long long k = (long long)b * n + i;
+        const float2 s = reinterpret_cast<const float2*>(score)[k];
+        const float2 zz = get_noise(z, b, i, k, key, offset);
+        const float ex = s.x * sd + zz.x, ey = s.y * sd + zz.y;
+        const double r2 = (double)ex * (double)ex + (double)ey * (double)ey;
+        acc += kind == 0 ? r2 : sqrt(r2);
+    }
+    loss_block_partial(acc, part);
+}
+// the predictive models' losses (model.py:329-343, 479-481), d = a - b in fp32: kind 0 sum d^2 over the n floats of a row (a complex
+// spectrogram through its float view, or a real waveform); kind 1 sum |d| over n complex elements; kind 2 sum |d| over n real samples.
+// With row_frames a row of kind 0 / 1 is complex (kind 0: n even) and counts the frames below row_frames[b] only.
+__global__ void pair_loss_kernel(double* __restrict__ part, const float* __restrict__ a, const float* __restrict__ b_,
+                                 const int* __restrict__ row_frames, long long n, int T, int kind) {
+    const int b = blockIdx.y;
+    const int frames = row_frames ? row_frames[b] : 0;
+    const bool cplx = kind == 1 || (kind == 0 && row_frames);
+    const long long ne = (kind == 0 && row_frames) ? n / 2 : n;          // elements of the row the loop walks
+    const long long base = (long long)b * ne;
+    double acc = 0.0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < ne; i += (long long)gridDim.x * blockDim.x) {
+        if (cplx) {
+            if (row_frames && (int)(i % T) >= frames) continue;
+            const float2 p = reinterpret_cast<const float2*>(a)[base + i], q = reinterpret_cast<const float2*>(b_)[base + i];
+            const float dx = p.x - q.x, dy = p.y - q.y;
+            const double r2 = (double)dx * (double)dx + (double)dy * (double)dy;
+            acc += kind == 0 ? r2 : sqrt(r2);
+        } else {
+            const float d = a[base + i] - b_[base + i];
+            acc += kind == 0 ? (double)d * (double)d : fabs((double)d);
+        }
+    }
+    loss_block_partial(acc, part);
+}
+__global__ void loss_rows_finish_kernel(const double* __restrict__ part, int nb, int B, float* __restrict__ out) {   // one thread per row, fixed order
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) { double s = 0.0; for (int i = 0; i < nb; ++i) s += part[(long long)b * nb + i]; out[b] = (float)(0.5 * s); }
+}
+
 static inline int ew_blocks(long long n) { long long b = (n + 255) / 256; return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b)); }
+// blocks per row of the loss reductions: a function of the row length ONLY
+static inline int loss_blocks(long long n) { const int b = ew_blocks(n); return b > STORM_RK_ROW_BLOCKS ? STORM_RK_ROW_BLOCKS : b; }
 
 }  // namespace storm
 
@@ -629,4 +717,81 @@ extern "C" int storm_si_sdr(const float* s, const float* s_hat, float* out, int 
     hipLaunchKernelGGL(si_sdr_kernel, dim3(B), dim3(256), 0, (hipStream_t)st, s, s_hat, out, n, stride_s, stride_hat, eps);
     STORM_LAUNCH_CHECK();
     return STORM_OK;
+}
+
+// ---- validation loss (see the kernels).  The *_rs forms as above; `form` / `kind` are checked here, the kernels trust them.
+template <class Key>
+static int launch_perturb(const float* x0, const float* y, const float* z, float* xt, const float* m_rows, const float* std_rows,
+                          int form, int B, long long n, Key key, uint64_t offset, storm_stream_t s) {
+    if (form == 0) return launch_rows(perturb_kernel<0, Key>, B, n, s, x0, y, z, xt, n, m_rows, std_rows, key, offset);
+    return launch_rows(perturb_kernel<1, Key>, B, n, s, x0, y, z, xt, n, m_rows, std_rows, key, offset);
+}
+extern "C" int storm_sde_perturb_rows(const float* x0, const float* y, const float* z, float* xt, const float* m_rows,
+                                      const float* std_rows, int form, int B, long long n, uint64_t seed, uint64_t offset,
+                                      storm_stream_t s) {
+    STORM_CHECK(x0 && y && xt && m_rows && std_rows && B > 0 && n > 0, "storm_sde_perturb_rows: bad arguments");
+    STORM_CHECK(form == 0 || form == 1, "storm_sde_perturb_rows: form=%d", form);
+    return launch_perturb(x0, y, z, xt, m_rows, std_rows, form, B, n, BatchKey{seed}, offset, s);
+}
+extern "C" int storm_sde_perturb_rows_rs(const float* x0, const float* y, const float* z, float* xt, const float* m_rows,
+                                         const float* std_rows, int form, int B, long long n, uint64_t seed, uint64_t offset,
+                                         const uint64_t* row_seeds, storm_stream_t s) {
+    (void)seed;
+    STORM_CHECK(row_seeds, "storm_sde_perturb_rows_rs: null row_seeds");
+    STORM_CHECK(x0 && y && xt && m_rows && std_rows && B > 0 && n > 0, "storm_sde_perturb_rows_rs: bad arguments");
+    STORM_CHECK(form == 0 || form == 1, "storm_sde_perturb_rows_rs: form=%d", form);
+    return launch_perturb(x0, y, z, xt, m_rows, std_rows, form, B, n, RowKeys{row_seeds}, offset, s);
+}
+
+extern "C" long long storm_dsm_loss_scratch_bytes(int B, long long n) {
+    if (B <= 0 || n <= 0) return 0;
+    return (long long)B * loss_blocks(n) * (long long)sizeof(double);
+}
+static int finish_loss_rows(const double* part, int nb, int B, float* out, storm_stream_t s) {
+    hipLaunchKernelGGL(loss_rows_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)s, part, nb, B, out);
+    STORM_LAUNCH_CHECK();
+    return STORM_OK;
+}
+template <class Key>
+static int launch_dsm_loss(const char* who, const float* score, const float* z, float* out, void* scratch, long long scratch_bytes,
+                           const float* std_rows, const int* row_frames, int T, int kind, int B, long long n, Key key,
+                           uint64_t offset, storm_stream_t s) {
+    STORM_CHECK(score && out && scratch && std_rows && B > 0 && n > 0, "%s: bad arguments", who);
+    STORM_CHECK(kind == 0 || kind == 1, "%s: kind=%d", who, kind);
+    STORM_CHECK(!row_frames || (T > 0 && n % T == 0), "%s: row_frames with T=%d for rows of %lld elements", who, T, n);
+    STORM_CHECK(scratch_bytes >= storm_dsm_loss_scratch_bytes(B, n), "%s: scratch of %lld bytes < %lld", who, scratch_bytes,
+                storm_dsm_loss_scratch_bytes(B, n));
+    const int nb = loss_blocks(n);
+    hipLaunchKernelGGL(dsm_loss_kernel<Key>, dim3(nb, B), dim3(256), 0, (hipStream_t)s, (double*)scratch, score, z, std_rows, row_frames, n, T,
+                       kind, key, offset);
+    return finish_loss_rows((const double*)scratch, nb, B, out, s);
+}
+extern "C" int storm_dsm_loss_rows(const float* score, const float* z, float* out, void* scratch, long long scratch_bytes,
+                                   const float* std_rows, const int* row_frames, int T, int kind, int B, long long n, uint64_t seed,
+                                   uint64_t offset, storm_stream_t s) {
+    return launch_dsm_loss("storm_dsm_loss_rows", score, z, out, scratch, scratch_bytes, std_rows, row_frames, T, kind, B, n, BatchKey{seed},
+                           offset, s);
+}
+extern "C" int storm_dsm_loss_rows_rs(const float* score, const float* z, float* out, void* scratch, long long scratch_bytes,
+                                      const float* std_rows, const int* row_frames, int T, int kind, int B, long long n, uint64_t seed,
+                                      uint64_t offset, const uint64_t* row_seeds, storm_stream_t s) {
+    (void)seed;
+    STORM_CHECK(row_seeds, "storm_dsm_loss_rows_rs: null row_seeds");
+    return launch_dsm_loss("storm_dsm_loss_rows_rs", score, z, out, scratch, scratch_bytes, std_rows, row_frames, T, kind, B, n,
+                           RowKeys{row_seeds}, offset, s);
+}
+
+extern "C" int storm_pair_loss_rows(const float* a, const float* b, float* out, void* scratch, long long scratch_bytes,
+                                    const int* row_frames, int T, int kind, int B, long long n, storm_stream_t s) {
+    STORM_CHECK(a && b && out && scratch && B > 0 && n > 0, "storm_pair_loss_rows: bad arguments");
+    STORM_CHECK(kind >= 0 && kind <= 2, "storm_pair_loss_rows: kind=%d", kind);
+    STORM_CHECK(!row_frames || kind != 2, "storm_pair_loss_rows: row_frames with real samples (kind 2)");
+    STORM_CHECK(!row_frames || kind != 0 || n % 2 == 0, "storm_pair_loss_rows: row_frames with an odd float count %lld", n);
+    const long long ne = (row_frames && kind == 0) ? n / 2 : n;           // complex elements of a row with frames
+    STORM_CHECK(!row_frames || (T > 0 && ne % T == 0), "storm_pair_loss_rows: row_frames with T=%d for rows of %lld elements", T, ne);
+    STORM_CHECK(scratch_bytes >= storm_dsm_loss_scratch_bytes(B, n), "storm_pair_loss_rows: scratch of %lld bytes < %lld", scratch_bytes,
+                storm_dsm_loss_scratch_bytes(B, n));
+    const int nb = loss_blocks(n);
+    hipLaunchKernelGGL(pair_loss_kernel, dim3(nb, B), dim3(256), 0, (hipStream_t)s, (double*)scratch, a, b, row_frames, n, T, kind);
+    return finish_loss_rows((const double*)scratch, nb, B, out, s);
 }

@@ -2,7 +2,8 @@
 DiscriminativeModel :320, StochasticRegenerationModel :392) without Lightning: ``enhance()``,
 ``get_pc_sampler()``, ``get_ode_sampler()``, ``forward`` / ``forward_score`` / ``forward_denoiser``,
 ``to_audio`` / ``_stft`` / ``_istft`` / ``_forward_transform`` / ``_backward_transform``,
-``eval(no_ema=False)`` EMA swap and ``load_from_checkpoint``.  Training methods are out of scope.
+``eval(no_ema=False)`` EMA swap and ``load_from_checkpoint``, and ``validation_loss`` - the reference's ``_step`` as
+``validation_step`` logs it (valid_loss), forward only.  Training methods are out of scope.
 
 New surface (not in the reference): ``enhance_batch`` (several utterances per call, equal to
 per-utterance ``enhance`` calls), ``set_precision`` and the ``noise_fn`` / ``seed`` / ``row_seeds`` sampler knobs.
@@ -170,6 +171,32 @@ class _Base(nn.Module):
         Y, peak = self.data_module.wav_to_spec(yd, pad_to=64, lengths=lengths)
         return Y, peak, y.size(1)
 
+    # ---- validation loss: the reference's `_step` (model.py:138-154, 345-349, 560-595) ------------
+    def _loss_draws(self, B, t, z, seed, row_seeds):
+        """(t fp32 [B] on the host, noise keywords of the perturbation and the loss kernel).  t = t_eps + (T - t_eps) u (model.py:144)
+        with u from a host generator seeded with `seed`, or - row_seeds - one generator per row, so that a row's t does not depend on
+        its batch; with neither, torch's global generator gives u and the kernels' seed, as it gives the reference its draws."""
+        if sum(v is not None for v in (z, seed, row_seeds)) > 1:
+            raise ValueError("z, seed and row_seeds exclude one another")
+        if row_seeds is not None:
+            row_seeds = [int(v) for v in row_seeds]
+            if len(row_seeds) != B:
+                raise ValueError(f"row_seeds has {len(row_seeds)} keys for a batch of {B} rows")
+        if t is None:
+            if row_seeds is not None:
+                u = torch.cat([torch.rand(1, generator=torch.Generator().manual_seed(v)) for v in row_seeds])
+            else:
+                u = torch.rand(B, generator=None if seed is None else torch.Generator().manual_seed(int(seed)))
+            t = self.t_eps + (self.sde.T - self.t_eps) * u
+        t = t.detach().to(device="cpu", dtype=torch.float32)
+        if t.shape != (B,):
+            raise ValueError(f"t has shape {tuple(t.shape)} for a batch of {B} rows")
+        if z is not None:
+            return t, {}
+        if row_seeds is not None:
+            return t, {"row_seeds": row_seeds}
+        return t, {"seed": int(seed) if seed is not None else int(torch.randint(2 ** 62, (1,)))}
+
     def _score_network(self):
         """the network whose evaluations a grouped stream shares (ScoreModel: dnn; StoRM: score_net - its denoiser runs once per micro-batch)"""
         return getattr(self, "score_net", None) or self.dnn
@@ -311,6 +338,25 @@ class ScoreModel(_Base):
         x_hat = self.data_module.spec_to_wav(sample, T_orig, peak, lengths=lengths)
         return (x_hat, nfe) if return_nfe else x_hat
 
+    def validation_loss(self, x, y, t=None, z=None, seed=None, row_seeds=None, frames=None, reduce=True):
+        """The reference's `_step` (model.py:138-154), the number it logs as valid_loss, on a spectrogram batch x (clean), y (noisy)
+        complex64 [B,1,F,T]: draw t, perturb x towards y (one kernel), ONE score evaluation, the residual loss of `loss_type`
+        (one kernel and a row sum).  t / z: injected (parity runs); otherwise t is drawn on the host and the noise in the kernels from
+        seed= or row_seeds= (see _loss_draws; with row_seeds row b is its batch-1 call with seed = row_seeds[b]).  frames: the rows'
+        valid frame counts - the padding frames of a ragged or padded batch stay out of the sums.  reduce=True: torch.mean of the
+        rows as `_loss` takes it (model.py:113-122); reduce=False: the rows, fp32 [B]."""
+        from . import ops
+        if self.loss_type not in ops.LOSS_KINDS:
+            raise NotImplementedError(f"loss_type {self.loss_type!r}: the score loss is 'mse' or 'mae' (model.py:113-122)")
+        th, keys = self._loss_draws(x.shape[0], t, z, seed, row_seeds)
+        with torch.no_grad():
+            x, y = x.to(self.device), y.to(self.device)
+            z = None if z is None else z.to(self.device)
+            x_t, std = self.sde.marginal_prob_sample(x, th, y, z=z, **keys)
+            score = self(x_t, th.to(self.device), y)
+            rows = ops.dsm_loss_rows(score, std, z=z, kind=self.loss_type, frames=frames, **keys)
+        return torch.mean(rows) if reduce else rows
+
     def enhance(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", N=50, corrector_steps=1,
                 snr=0.5, timeit=False, scale_factor=None, return_stft=False, **kwargs):
         """One-call enhancement of one utterance y [1, L] (model.py:273-310)."""
@@ -343,6 +389,34 @@ class DiscriminativeModel(ScoreModel):
         t = torch.ones(y.shape[0], device=y.device)
         return self.dnn(y, t)
 
+    def validation_loss(self, x, y, frames=None, reduce=True):
+        """The reference's `_step` / `_loss` (model.py:329-349): Xhat = self(y), then `loss_type` 'mse' / 'mae' / 'sisdr' against x
+        (spectrogram batches complex64 [B,1,F,T]).  A time-domain backbone (FORCE_STFT_OUT) returns waveforms: x goes through
+        istft(spec_back(x)) first, as upstream; 'sisdr' trims to the shorter length (si_sdr_torch), 'mse' / 'mae' on unequal
+        lengths fail as upstream's subtraction does.  reduce=True: torch.mean over the rows; reduce=False: the rows, fp32 [B]."""
+        from . import ops
+        time_domain = bool(getattr(self.dnn, "FORCE_STFT_OUT", False))
+        if self.loss_type not in ("mse", "mae", "sisdr"):
+            raise NotImplementedError(f"loss_type {self.loss_type!r}: the predictive loss is 'mse', 'mae' or 'sisdr' (model.py:329-343)")
+        with torch.no_grad():
+            x, y = x.to(self.device), y.to(self.device)
+            x_hat = self(y)
+            if time_domain:
+                if frames is not None:
+                    raise ValueError("frames count spectrogram frames: a time-domain backbone's loss runs on waveforms")
+                x = self._istft(self._backward_transform(x.squeeze(1)))
+                x_hat = x_hat.reshape(x_hat.shape[0], -1)
+            if self.loss_type == "sisdr":
+                if not time_domain:
+                    raise RuntimeError("loss_type 'sisdr' needs a time-domain backbone (si_sdr_torch takes 1-D signals, util/other.py:88-94)")
+                rows = -ops.si_sdr(x.float(), x_hat.float(), eps=1e-10)
+            else:
+                if x.shape != x_hat.shape:
+                    raise RuntimeError(f"The size of tensor a ({x.shape[-1]}) must match the size of tensor b ({x_hat.shape[-1]}) for "
+                                       f"loss_type {self.loss_type!r}: target {tuple(x.shape)}, estimate {tuple(x_hat.shape)}")
+                rows = ops.pair_loss_rows(x, x_hat, kind=self.loss_type, frames=frames)
+        return torch.mean(rows) if reduce else rows
+
     def enhance(self, y, **ignored_kwargs):
         with torch.no_grad():
             Y, peak, T_orig = self._prepare(y)
@@ -373,6 +447,8 @@ class StochasticRegenerationModel(_Base):
         self.ema = _EMA(self.parameters(), decay=ema_decay)
         self.condition, self.mode = condition, mode
         self.lr, self.num_eval_files, self.nolog = lr, num_eval_files, nolog
+        self.loss_type_denoiser, self.loss_type_score = loss_type_denoiser, loss_type_score
+        self.weighting_denoiser_to_score = kwargs.get("weighting_denoiser_to_score", .5)       # model.py:438-441
 
     def forward_score(self, x, t, score_conditioning, sde_input, **kwargs):
         """-score_net(cat[x] + conditioning, t)  (model.py:548-554)"""
@@ -395,6 +471,43 @@ class StochasticRegenerationModel(_Base):
                                                y=y[sl], conditioning=[c[sl] for c in conditioning], **self._slice_keys(kwargs, sl)),
             y, minibatch)
 
+    def _score_conditioning(self, Y, Y_denoised):
+        if self.condition == "noisy":
+            return [Y]
+        if self.condition == "post_denoiser":
+            return [Y_denoised]
+        if self.condition == "both":
+            return [Y, Y_denoised]
+        raise NotImplementedError(f"Don't know the conditioning you have wished for: {self.condition}")
+
+    def validation_loss(self, x, y, t=None, z=None, seed=None, row_seeds=None, frames=None, reduce=True):
+        """The reference's `_step` (model.py:560-595): denoiser forward, the forward SDE from x towards y_denoised, `condition`,
+        forward_score, then (loss, loss_score, loss_denoiser) with loss = w loss_denoiser + (1 - w) loss_score, w =
+        weighting_denoiser_to_score; loss_denoiser is None for loss_type_denoiser 'none'.  Arguments as ScoreModel.validation_loss.
+        The reduction is the reference's `_reduce_op`, 0.5 * torch.sum over the WHOLE batch (model.py:449) - the sum of the rows,
+        not their mean; reduce=False: the rows, fp32 [B]."""
+        from . import ops
+        if self.loss_type_score not in ops.LOSS_KINDS:                    # configure_losses (model.py:465-485)
+            raise NotImplementedError(f"loss_type_score {self.loss_type_score!r}: 'mse' or 'mae'")
+        if self.loss_type_denoiser not in ("mse", "mae", "none"):
+            raise NotImplementedError(f"loss_type_denoiser {self.loss_type_denoiser!r}: 'mse', 'mae' or 'none'")
+        th, keys = self._loss_draws(x.shape[0], t, z, seed, row_seeds)
+        with torch.no_grad():
+            x, y = x.to(self.device), y.to(self.device)
+            z = None if z is None else z.to(self.device)
+            y_denoised = self.forward_denoiser(y)
+            x_t, std = self.sde.marginal_prob_sample(x, th, y_denoised, z=z, **keys)
+            score = self.forward_score(x_t, th.to(self.device), self._score_conditioning(y, y_denoised), y_denoised)
+            ls = ops.dsm_loss_rows(score, std, z=z, kind=self.loss_type_score, frames=frames, **keys)
+            ld = None
+            if self.loss_type_denoiser != "none":
+                ld = ops.pair_loss_rows(y_denoised, x, kind=self.loss_type_denoiser, frames=frames)
+            if reduce:
+                ls, ld = torch.sum(ls), (None if ld is None else torch.sum(ld))
+            w = self.weighting_denoiser_to_score
+            loss = ls if ld is None else w * ld + (1 - w) * ls                                  # model.py:533-543
+        return loss, ls, ld
+
     def enhance_batch(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="none", N=30,
                       corrector_steps=1, snr=0.5, denoiser_only=False, return_nfe=False, return_stft=False, lengths=None,
                       row_seeds=None, **kwargs):
@@ -407,14 +520,7 @@ class StochasticRegenerationModel(_Base):
         with torch.no_grad():
             Y_denoised = self.forward_denoiser(Y) if self.denoiser_net is not None else None
             if self.score_net is not None and not denoiser_only:
-                if self.condition == "noisy":
-                    score_conditioning = [Y]
-                elif self.condition == "post_denoiser":
-                    score_conditioning = [Y_denoised]
-                elif self.condition == "both":
-                    score_conditioning = [Y, Y_denoised]
-                else:
-                    raise NotImplementedError(f"Don't know the conditioning you have wished for: {self.condition}")
+                score_conditioning = self._score_conditioning(Y, Y_denoised)
                 if sampler_type != "pc":
                     raise NotImplementedError("StoRM supports the PC sampler only (the reference's ODE path drops the "
                                               "conditioning, model.py:671-691)")

@@ -496,6 +496,72 @@ def sde_pf_drift_rows(x, y, score, a_rows, g_rows):
     return out
 
 
+# ---------------------------------------------------------------- validation loss ---------
+LOSS_KINDS = {"mse": 0, "mae": 1}
+PAIR_SQUARE, PAIR_ABS_COMPLEX, PAIR_ABS_REAL = 0, 1, 2
+
+
+def sde_perturb_rows(x0, y, m_rows, std_rows, form, z=None, seed=0, offset=0, row_seeds=None):
+    """x_t = mean_b(x0, y) + std_b z on complex64 [B, ...] in one pass (SDE.marginal_prob + model.py:144-150).  m_rows / std_rows: fp32 [B]
+    in the SDE's own expressions; form 0: m x0 + (1 - m) y (OUVESDE._mean), form 1: y + m (x0 - y) (OUVPSDE._mean); z=None draws in-kernel."""
+    if x0.shape != y.shape or (z is not None and z.shape != x0.shape):
+        raise ValueError(f"sde_perturb_rows: x0 {tuple(x0.shape)}, y {tuple(y.shape)}, z {None if z is None else tuple(z.shape)}")
+    x0, y, z = x0.contiguous(), y.contiguous(), (None if z is None else z.contiguous())
+    xt = torch.empty_like(x0)
+    m, sd = _rows32(m_rows, x0), _rows32(std_rows, x0)
+    _noise_call("storm_sde_perturb_rows", (L.ptr(_r(x0)), L.ptr(_r(y)), L.ptr(_r(z)), L.ptr(_r(xt)), L.ptr(m), L.ptr(sd), int(form), x0.shape[0],
+                                           _n_per_batch(x0)), seed, offset, row_seeds, x0)
+    return xt
+
+
+def _frames(frames, like):
+    """(row_frames device int32 [B] or None, T): `like` is a spectrogram batch [B, ..., T]"""
+    rf = _row_len(frames, like)
+    if rf is not None and rf.shape[0] != like.shape[0]:
+        raise ValueError(f"frames has {rf.shape[0]} entries for a batch of {like.shape[0]} rows")
+    return rf, (like.shape[-1] if rf is not None else 0)
+
+
+def _loss_scratch(B, n, like):
+    # per call (the caching allocator makes it cheap), not cached per host thread: ADVICE.md - such a cache is never freed
+    return torch.empty((L.lib().storm_dsm_loss_scratch_bytes(B, n),), dtype=torch.uint8, device=like.device)
+
+
+def dsm_loss_rows(score, std_rows, z=None, kind="mse", frames=None, seed=0, offset=0, row_seeds=None):
+    """fp32 [B]: row b's 0.5 sum rho(score std_b + z), rho = |.|^2 ('mse') or |.| ('mae') (model.py:151-153, 113-122).  z=None re-draws
+    the noise of the perturbation with the same seed / offset / row_seeds in the kernel.  frames: per-row valid frame counts of
+    spectrogram rows [..., T] (the rest of a row is padding and stays out)."""
+    score, z = score.contiguous(), (None if z is None else z.contiguous())
+    B, n = score.shape[0], _n_per_batch(score)
+    out = _alloc((B,), torch.float32, score)
+    sd = _rows32(std_rows, score)
+    rf, T = _frames(frames, score)
+    ws = _loss_scratch(B, n, score)
+    _noise_call("storm_dsm_loss_rows", (L.ptr(_r(score)), L.ptr(_r(z)), L.ptr(out), L.ptr(ws), ws.numel(), L.ptr(sd), L.ptr(rf), T,
+                                        LOSS_KINDS[kind], B, n), seed, offset, row_seeds, score)
+    return out
+
+
+def pair_loss_rows(a, b, kind="mse", frames=None):
+    """fp32 [B]: row b's 0.5 sum |a - b|^2 ('mse') or 0.5 sum |a - b| ('mae') of two complex spectrogram batches or two real waveform
+    batches of one shape (DiscriminativeModel._loss model.py:329-343, loss_fn_denoiser :479-481); frames as in dsm_loss_rows (complex only)."""
+    if a.shape != b.shape or a.is_complex() != b.is_complex():
+        raise ValueError(f"pair_loss_rows: {tuple(a.shape)} {a.dtype} against {tuple(b.shape)} {b.dtype}")
+    cplx = a.is_complex()
+    if frames is not None and not cplx:
+        raise ValueError("pair_loss_rows: frames count the frames of complex spectrogram rows")
+    B = a.shape[0]
+    av, bv = (_r(a.contiguous()), _r(b.contiguous())) if cplx else (a.float().contiguous(), b.float().contiguous())
+    code = PAIR_SQUARE if LOSS_KINDS[kind] == 0 else (PAIR_ABS_COMPLEX if cplx else PAIR_ABS_REAL)
+    n = _n_per_batch(av) if code != PAIR_ABS_COMPLEX else _n_per_batch(a)
+    out = _alloc((B,), torch.float32, av)
+    rf, T = _frames(frames, a)
+    ws = _loss_scratch(B, n, av)
+    L.check(L.lib().storm_pair_loss_rows(L.ptr(av), L.ptr(bv), L.ptr(out), L.ptr(ws), ws.numel(), L.ptr(rf), T, code, B, n, L.stream()),
+            "storm_pair_loss_rows")
+    return out
+
+
 _rk_scratch = {}
 
 

@@ -68,6 +68,15 @@ class SDE(abc.ABC):
         """the probability-flow right-hand side a(t_b) (y - x) - 1/2 g(t_b)^2 score (t_host: fp32 [B] on the host)"""
         return ops.sde_pf_drift_rows(x, y, score, self.drift_rows(t_host), self.diffusion(t_host))
 
+    def marginal_prob_sample(self, x0, t, y, z=None, **keys):
+        """One draw of the forward process, x_t = mean(x0, t, y) + std(t) z (marginal_prob + model.py:144-150), in ONE fused kernel
+        on the state (storm_sde_perturb_rows: no `mean` tensor; z=None draws in-kernel from seed= / offset= / row_seeds=).  The
+        per-row factors are the reference's fp32 torch expressions (`mean_factor_rows`, `_std`) evaluated on the host copy of t
+        [B], so they are the same numbers on every device.  Returns (x_t, std_rows fp32 [B] on x0's device)."""
+        th = t.detach().to(device="cpu", dtype=torch.float32)
+        std = self._std(th).to(x0.device)
+        return ops.sde_perturb_rows(x0, y, self.mean_factor_rows(th), std, self.MEAN_FORM, z=z, **keys), std
+
     def reverse(oself, score_model, probability_flow=False, diffusion_power_gradient=None):
         """Reverse-time SDE/ODE (sdes.py:92-159).  diffusion_power_gradient(x, t): subtracted from the total drift when the
         diffusion depends on the state (sdes.py:98-99, 137-138); None for both registered SDEs."""
@@ -143,6 +152,12 @@ class OUVESDE(SDE):
         e = torch.exp(-self.theta * t)[:, None, None, None]
         return e * x0 + (1 - e) * y
 
+    MEAN_FORM = 0                                      # storm_sde_perturb_rows: m x0 + (1 - m) y
+
+    def mean_factor_rows(self, t):
+        """exp(-theta t), the weight of x0 in `_mean` (sdes.py:210-213)"""
+        return torch.exp(-self.theta * t)
+
     def _std(self, t, **kwargs):
         sigma_min, theta, logsig = self.sigma_min, self.theta, self.logsig
         return torch.sqrt((sigma_min ** 2 * torch.exp(-2 * theta * t) * (torch.exp(2 * (theta + logsig) * t) - 1) * logsig)
@@ -216,6 +231,13 @@ class OUVPSDE(SDE):
         b0, b1, s = self.beta_min, self.beta_max, self.stiffness
         x0y_fac = torch.exp(-0.25 * s * t * (t * (b1 - b0) + 2 * b0))[:, None, None, None]
         return y + x0y_fac * (x0 - y)
+
+    MEAN_FORM = 1                                      # storm_sde_perturb_rows: y + m (x0 - y)
+
+    def mean_factor_rows(self, t):
+        """the weight of x0 - y in `_mean` (sdes.py:296-299)"""
+        b0, b1, s = self.beta_min, self.beta_max, self.stiffness
+        return torch.exp(-0.25 * s * t * (t * (b1 - b0) + 2 * b0))
 
     def _std(self, t, **kwargs):
         b0, b1, s = self.beta_min, self.beta_max, self.stiffness

@@ -9,6 +9,7 @@ implementations of ITU-T P.862 / ESTOI; without them the two averages are NaN).
 
 Pairs come from `model.data_module.valid_set.__getitem__(i, raw=True)` like the reference, or from `pairs=` (a sequence
 of (clean [1, L], noisy [1, L]) tensors) since datasets are outside the hot path."""
+import inspect
 import math
 
 import torch
@@ -86,3 +87,36 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
         k = min(n, MAX_VIS_SAMPLES)
         audios = [[pairs[i][1][0] for i in range(k)], [est[i] for i in range(k)], [pairs[i][0][0] for i in range(k)]]
     return _pesq, float(sdr.mean()) if n else math.nan, _estoi, specs, audios
+
+
+def validation_epoch(model, batches, seed=None, row_seeds=None, **loss_kwargs):
+    """valid_loss over a validation set: `model.validation_loss` (the reference's `_step` as validation_step logs it, model.py:161-163,
+    605-610) on every micro-batch of `batches` = [(x, y) or (x, y, frames), ...] - spectrogram batches complex64 [b,1,F,T], frames the
+    rows' valid frame counts - and the mean of the batch losses weighted by their row counts, as Lightning reduces a value logged with
+    on_epoch=True and batch_size.  seed: micro-batch k draws from seed + k (as enhance_stream); row_seeds: one key list per micro-batch.
+    Returns a float, or for StochasticRegenerationModel the tuple (loss, loss_score, loss_denoiser) of floats (loss_denoiser None for
+    loss_type_denoiser 'none')."""
+    model.eval()
+    batches = list(batches)
+    if row_seeds is not None and len(row_seeds) != len(batches):
+        raise ValueError(f"row_seeds has {len(row_seeds)} key lists for {len(batches)} micro-batches")
+    draws = "seed" in inspect.signature(model.validation_loss).parameters          # (DiscriminativeModel draws nothing)
+    totals, rows = None, 0
+    for k, batch in enumerate(batches):
+        kw = dict(loss_kwargs)
+        if len(batch) == 3:
+            kw["frames"] = batch[2]
+        if draws and row_seeds is not None:
+            kw["row_seeds"] = row_seeds[k]
+        elif draws and seed is not None:
+            kw["seed"] = seed + k
+        out = model.validation_loss(batch[0], batch[1], **kw)
+        vals = out if isinstance(out, tuple) else (out,)
+        b = batch[0].shape[0]
+        vals = [None if v is None else float(v) * b for v in vals]
+        totals = vals if totals is None else [None if v is None else s + v for s, v in zip(totals, vals)]
+        rows += b
+    if totals is None:
+        return math.nan
+    means = tuple(None if s is None else s / rows for s in totals)
+    return means if len(means) > 1 else means[0]
