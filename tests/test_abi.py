@@ -25,11 +25,50 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert lib.storm_abi_version() == 2
     lib.storm_last_error.restype = ctypes.c_char_p
     assert lib.storm_last_error() is not None
+    # the sizes the binding refuses a library by (storm_abi_struct_bytes), asked of the library directly
+    from storm_amd import _lib
+    lib.storm_abi_struct_bytes.restype, lib.storm_abi_struct_bytes.argtypes = ctypes.c_longlong, [ctypes.c_int]
+    for which, cls in enumerate((_lib.ConvArgs, _lib.Op, _lib.ConvSeg, _lib.NcsnppConfig, _lib.NcsnppConfigEx)):
+        assert lib.storm_abi_struct_bytes(which) == ctypes.sizeof(cls), cls.__name__
+    assert lib.storm_abi_struct_bytes(5) == -1 and lib.storm_abi_struct_bytes(-1) == -1
 
 
 def test_python_binding_covers_the_header():
     from storm_amd import _lib
     assert set(declared_symbols()) == set(_lib.EXPORTS)
+
+
+# exported entry points that neither the product's Python nor a test calls (each with the reason it has no caller yet); a name that
+# is not listed here must occur in storm_amd/ (outside the binding table itself) or in tests/
+KNOWN_UNREACHED = [
+    "storm_gn_apply_kernel_name",    # bench.py's per-op table only: the name of the kernel the GroupNorm-apply launcher picks
+    "storm_ncsnpp_arena",            # bench.py's per-op table and tools/tune_dispatch.py only: the parameter arena behind a planned program
+]
+
+
+def test_every_export_is_reached_by_the_product_or_a_test():
+    """An entry point that nothing calls is a kernel that nothing checks: every name of _lib.EXPORTS occurs (as a whole word) in the
+    Python of storm_amd/ outside _lib.py or in a file under tests/.  The per-row-key forms are called as name + "_rs" by
+    ops._noise_call: such a name counts as reached where its base name is handed to _noise_call."""
+    import glob
+
+    from storm_amd import _lib
+    files = [f for f in glob.glob(os.path.join(ROOT, "storm_amd", "**", "*.py"), recursive=True) if os.path.basename(f) != "_lib.py"]
+    for ext in ("py", "c", "h", "cpp"):
+        files += glob.glob(os.path.join(ROOT, "tests", "**", "*." + ext), recursive=True)
+    words = set()
+    for f in files:
+        text = open(f).read()
+        if os.path.abspath(f) == os.path.abspath(__file__):
+            text = re.sub(r"KNOWN_UNREACHED = \[.*?\n\]", "", text, flags=re.S)       # (the list itself is no caller)
+        words |= set(re.findall(r"\bstorm_[a-z0-9_]+\b", text))
+    ops_text = open(os.path.join(ROOT, "storm_amd", "ops.py")).read()
+    noise_calls = set(re.findall(r"_noise_call\(\s*\"(storm_[a-z0-9_]+)\"", ops_text))
+    assert 'name + "_rs"' in ops_text and noise_calls
+    reached = words | {n + "_rs" for n in noise_calls}
+    unreached = sorted(n for n in _lib.EXPORTS if n not in reached)
+    assert unreached == sorted(KNOWN_UNREACHED), unreached
+    assert not set(KNOWN_UNREACHED) & reached                          # (a listed name that has found a caller leaves the list)
 
 
 def test_product_does_not_import_the_oracle():
@@ -87,6 +126,30 @@ def test_c_host_runs_a_forward_through_the_whole_network_abi(tmp_path, golden):
 
 
 import pytest  # noqa: E402
+
+from tests.backend import dev  # noqa: E402,F401
+
+
+def test_device_info(dev):
+    """storm_device_info: the architecture name (truncated to the caller's buffer, always terminated), the compute units and the memory
+    of the current device - torch's own numbers on the GPU, the host simulation's placeholders otherwise; every output is optional"""
+    import torch
+
+    from storm_amd import _lib
+    lib = _lib.lib()
+    name, n_cu, hbm = ctypes.create_string_buffer(b"\xff" * 64, 64), ctypes.c_int(-1), ctypes.c_size_t(1)
+    _lib.check(lib.storm_device_info(name, 64, ctypes.byref(n_cu), ctypes.byref(hbm)), "storm_device_info")
+    if dev.type == "cpu":
+        assert (name.value, n_cu.value, hbm.value) == (b"host-sim", 0, 0)
+    else:
+        p = torch.cuda.get_device_properties(dev)
+        assert name.value.decode() == p.gcnArchName and name.value.startswith(b"gfx950")
+        assert n_cu.value == p.multi_processor_count > 0 and hbm.value == p.total_memory > 0
+    short = ctypes.create_string_buffer(b"\xff" * 8, 8)
+    _lib.check(lib.storm_device_info(short, 4, None, None), "storm_device_info")
+    assert short.raw[:4] == name.value[:3] + b"\0" and short.raw[4:] == b"\xff" * 4
+    _lib.check(lib.storm_device_info(None, 0, None, None), "storm_device_info")
+
 
 
 @pytest.mark.gpu
