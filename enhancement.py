@@ -4,9 +4,9 @@
     python enhancement.py --test_dir noisy/ --enhanced_dir out/ --ckpt model.ckpt --mode storm \
         [--corrector ald --corrector-steps 1 --snr 0.5 --N 50]
 
-Additions: --precision {fp32,bf16}, --batch (equal-length utterances per sampler call), --seed / --utterance-seed and multi-GPU
-sharding when launched with torchrun (one process per GPU, files dealt by length; no collectives in the
-sampler).  WAV I/O uses scipy.io.wavfile (torchaudio is not required)."""
+Additions: --precision {fp32,bf16}, --batch (equal-length utterances per sampler call), --seed / --utterance-seed, --resample /
+--output-sr (files of other rates than 16 kHz, resampled on the device) and multi-GPU sharding when launched with torchrun (one
+process per GPU, files dealt by length; no collectives in the sampler).  WAV I/O uses scipy.io.wavfile (torchaudio is not required)."""
 import glob
 import hashlib
 import os
@@ -63,6 +63,10 @@ def main():
                    "(storm_amd.set_batch_invariant: launch decisions per image; costs the batch-aware kernel selections)")
     p.add_argument("--group", type=int, default=8, help="score-only and storm modes: this many micro-batches (frame buckets of different lengths) run their samplers in lockstep "
                    "and share the launches of the score network (ScoreModel.enhance_stream); 1 = one micro-batch after the other")
+    p.add_argument("--resample", action="store_true", help="(extension) read files of any sample rate: each is resampled to the model's 16 kHz on the device when it is loaded "
+                   "(SpecsDataModule.resample, scipy.signal.resample_poly's filter), batching and seeding work on the 16 kHz signals, and every enhanced file is "
+                   "resampled back and written at its own rate with its own sample count.  Without it a file of another rate is refused, as upstream")
+    p.add_argument("--output-sr", choices=("input", "model"), default="input", help="with --resample: write every file at its own rate (input) or at 16 kHz (model)")
     p.add_argument("--dist-world1", action="store_true", help="with ONE rank: form the RCCL process group anyway (dry run of the sharded path on one GPU)")
     args = p.parse_args()
     if args.seed is not None and args.utterance_seed is not None:
@@ -88,13 +92,27 @@ def main():
         storm_amd.set_batch_invariant(True)
 
     files = sorted(glob.glob(os.path.join(args.test_dir, "*.wav")))
-    wavs, lengths = [], []
+    model_sr = model.data_module.sample_rate
+    wavs, lengths, rates, samples = [], [], [], []
     for f in files:
         y, sr = read_wav(f)
-        assert sr == 16000, "You need to make sure sample_sr matches model_sr --> resample to 16kHz"
+        if not args.resample:
+            assert sr == 16000, "You need to make sure sample_sr matches model_sr --> resample to 16kHz"
+        rates.append(sr)
+        samples.append(y.shape[1])                          # the file's own sample count: what its enhanced file has again
         wavs.append(y[:1])
-        lengths.append(y.shape[1])
+        lengths.append(-(-y.shape[1] * model_sr // sr))     # ... and its count at the model's rate, which the files are dealt and bucketed by
+
+    def write_enhanced(i, x):
+        """file i's enhanced 16 kHz signal: back at the file's own rate and sample count (--output-sr input), or as it is"""
+        x, sr = x.float().reshape(-1), model_sr
+        if rates[i] != model_sr and args.output_sr == "input":
+            x, sr = model.data_module.resample(x.to(model.device), model_sr, rates[i])[:samples[i]], rates[i]
+        write_wav(os.path.join(args.enhanced_dir, os.path.basename(files[i])), x, sr)
     mine = D.shard_indices(len(files), rank, world, lengths)
+    for i in mine:
+        if rates[i] != model_sr:                            # --resample: this rank's files to the model's rate, on its device
+            wavs[i] = model.data_module.resample(wavs[i].to(model.device), rates[i], model_sr).cpu()
     # micro-batches of utterances that share a padded frame count (different lengths welcome): equal to per-file runs
     def run(batch):
         ids = [mine[k] for k in batch]
@@ -132,12 +150,12 @@ def main():
                                     row_seeds=None if keys is None else [[keys[i] for i in ids] for ids, _ in metas], **skw)
         for (ids, lens), x_hat in zip(metas, outs):
             for k, i in enumerate(ids):
-                write_wav(os.path.join(args.enhanced_dir, os.path.basename(files[i])), x_hat[k, :lens[k]].float().reshape(-1), 16000)
+                write_enhanced(i, x_hat[k, :lens[k]])
         buckets = []
     for batch in buckets:
         ids, outs = run(batch)
         for i, x in zip(ids, outs):
-            write_wav(os.path.join(args.enhanced_dir, os.path.basename(files[i])), x.float().reshape(-1), 16000)
+            write_enhanced(i, x)
     D.finish()
 
 

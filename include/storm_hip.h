@@ -464,6 +464,30 @@ int storm_istft(const float* spec, const float* peak, float* wav, float* frames,
                 const int* row_len, storm_stream_t s);
 
 /* ------------------------------------------------------------------------------------------
+ * Rational resampling (audio at another rate than the model's 16 kHz): x [B][L_in] at rate sr_in -> y [B][L_out] at sr_out with
+ * up / down = sr_out / sr_in REDUCED (g = gcd(sr_in, sr_out), up = sr_out / g, down = sr_in / g), L_out = ceil(L_in up / down):
+ *   R = max(up, down), half = 10 R;  h[j], j = 0 .. 2 half: the Kaiser(beta = 5) windowed-sinc low-pass with cut-off 1 / R of
+ *   Nyquist, normalised to unit DC gain, times up;
+ *   y[n] = sum_k h[n down - k up + half] x[k]        (x = 0 outside [0, L_in), h = 0 outside [0, 2 half])
+ * i.e. scipy.signal.resample_poly(x, up, down) with its defaults.  Polyphase: c = n down + half, p = c mod up, q = c div up,
+ * y[n] = sum_{m < M_p} T[p][m] x[q - m] with T[p][m] = h[p + m up] - one fp32 FMA chain over m ascending per output, so an
+ * output's bits depend on its own row's samples only.  Refused: a ratio that is not reduced, max(up, down) > 1024.
+ *
+ * storm_resample_num_taps: 2 half + 1 (< 0: refused).  The phase-major table has M = ceil(num_taps / up) taps per phase.
+ * storm_resample_taps (host): designs h in fp64 (I0 by its power series), rounds every tap to fp32 once and writes T as
+ *   fp32 [up][M], zero past M_p, into the CALLER's host memory of `capacity` floats (>= up M) - the single source of the
+ *   coefficients; the caller copies the table to the device.
+ * storm_resample_poly: taps = that table on the device.  row_len (optional, device int32 [B]): the rows' own input sample
+ *   counts; row b then gets ceil(row_len[b] up / down) outputs, the rest of its output row is zero, and its input samples at
+ *   k >= row_len[b] are never read.  One workgroup computes STORM_RESAMPLE_TILE outputs of one row. */
+#define STORM_RESAMPLE_MAX_RATE 1024
+#define STORM_RESAMPLE_TILE 1024
+int storm_resample_num_taps(int up, int down);
+int storm_resample_taps(int up, int down, float* taps_phase_major, long long capacity);
+int storm_resample_poly(const float* x, float* y, const float* taps, int B, long long L_in, long long stride_in,
+                        long long L_out, long long stride_out, const int* row_len, int up, int down, storm_stream_t s);
+
+/* ------------------------------------------------------------------------------------------
  * ConvTasNet (backbones/convtasnet.py): the time-domain denoiser.  Activations are channels-last [B][L][C] in `dtype`
  * (C % 8 == 0); the TCN's running sums `output` / `skip_connection` are fp32 [B][L][BN]; statistics are fp32.  A global layer
  * norm (GroupNorm(1, C, eps) over all of C x L of a row) is never materialised: the producing kernel writes per-wave

@@ -20,6 +20,7 @@ _DT2TORCH = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
 OP_NPTR, OP_NINT, OP_NFLT = 13, 24, 4
 ABI_VERSION = 2                  # include/storm_hip.h: STORM_ABI_VERSION
+RESAMPLE_TILE = 1024             # include/storm_hip.h: STORM_RESAMPLE_TILE, the outputs one workgroup of storm_resample_poly computes
 
 
 class StormError(RuntimeError):
@@ -139,6 +140,9 @@ _SIGNATURES = {
     "storm_peak_abs": ([_vp, _vp, _i, _ll, _ll, _vp, _vp], C.c_int),
     "storm_stft": ([_vp, _vp, _vp, _vp, _vp, _i, _ll, _ll, _i, _i, _i, _i, _f, _f, _vp, _vp], C.c_int),
     "storm_istft": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _ll, _ll, _i, _i, _f, _f, _vp, _vp], C.c_int),
+    "storm_resample_num_taps": ([_i, _i], C.c_int),
+    "storm_resample_taps": ([_i, _i, _vp, _ll], C.c_int),
+    "storm_resample_poly": ([_vp, _vp, _vp, _i, _ll, _ll, _ll, _ll, _vp, _i, _i, _vp], C.c_int),
     "storm_tasnet_num_partials": ([_i, _i, _i], C.c_int),
     "storm_tasnet_frames": ([_ll, _i], C.c_int),
     "storm_tasnet_encode": ([_vp, _ll, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp], C.c_int),

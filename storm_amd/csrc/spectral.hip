@@ -145,6 +145,86 @@ __global__ void spec_transform_kernel(const float* __restrict__ in, float* __res
     }
 }
 
+// ---- rational resampling (storm_resample_poly; definition in include/storm_hip.h) ---------------------------------------------
+// y[n] = sum_m T[p][m] x[q - m],  c = n down + half, p = c mod up, q = c div up,  T = the phase-major table of storm_resample_taps.
+// One workgroup owns RESAMPLE_TILE consecutive outputs of one row (thread t: outputs t, t + 256, ...: coalesced stores, and for
+// the common odd `down` a conflict-free LDS stride).  The input samples its outputs touch are staged through LDS in windows of
+// RESAMPLE_WINDOW samples, walked from the highest index down: that is ascending m for every output, so an output is ONE fp32 FMA
+// chain over m = 0 .. M_p - 1 whatever the window, tile, batch or grid - its bits depend on its own row's samples only.  (A tile of
+// 48 -> 16 kHz or 44.1 -> 16 kHz needs one window; ratios of 8 : 1 and steeper walk several.)  Samples outside [0, len_b) are zero
+// and are never loaded; products with them are skipped (they add +0).  The taps stay in global memory: an output's M_p taps are
+// contiguous, the table is <= 82 KB and lives in the L2.
+constexpr int RESAMPLE_TILE = STORM_RESAMPLE_TILE, RESAMPLE_THREADS = 256, RESAMPLE_PER_THREAD = RESAMPLE_TILE / RESAMPLE_THREADS;
+constexpr int RESAMPLE_WINDOW = 8192;            // samples per staged window (32 KB of LDS, a multiple of 4)
+
+__global__ void __launch_bounds__(RESAMPLE_THREADS)
+resample_poly_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ taps, long long L_in, long long stride_in,
+                     long long L_out, long long stride_out, const int* __restrict__ row_len, int up, int down, int half, int M) {
+    __shared__ __attribute__((aligned(16))) float xs[RESAMPLE_WINDOW];
+    const int b = blockIdx.y, t = threadIdx.x;
+    long long len = row_len ? (long long)row_len[b] : L_in;
+    if (len > L_in) len = L_in;                                                      // (a device-side length the host never saw must still not read outside the row)
+    const long long n_valid = len <= 0 ? 0 : (len * up + down - 1) / down;           // this row's outputs; the rest of its row is zero
+    const long long n0 = (long long)blockIdx.x * RESAMPLE_TILE;
+    const float* xr = x + (long long)b * stride_in;
+    float* yr = y + (long long)b * stride_out;
+    const bool vec = ((uintptr_t)xr & 15) == 0;                                      // 16-byte loads where the row starts on one
+
+    long long q[RESAMPLE_PER_THREAD];
+    int Mp[RESAMPLE_PER_THREAD];
+    const float* tp[RESAMPLE_PER_THREAD];
+    float acc[RESAMPLE_PER_THREAD];
+#pragma unroll
+    for (int j = 0; j < RESAMPLE_PER_THREAD; ++j) {
+        const long long n = n0 + j * RESAMPLE_THREADS + t;
+        const long long c = n * down + half;
+        const int p = (int)(c % up);
+        q[j] = c / up;
+        Mp[j] = n < n_valid ? (2 * half - p) / up + 1 : 0;                           // taps of phase p: h[p + m up], p + m up <= 2 half
+        tp[j] = taps + (long long)p * M;
+        acc[j] = 0.f;
+    }
+    if (n0 < n_valid) {                                                              // (uniform in the workgroup: b and blockIdx only)
+        const long long n_last = (n0 + RESAMPLE_TILE < n_valid ? n0 + RESAMPLE_TILE : n_valid) - 1;
+        long long hi = (n_last * down + half) / up;                                  // highest sample any output of the tile reads (m = 0)
+        if (hi > len - 1) hi = len - 1;
+        long long lowest = (n0 * down + half) / up - (M - 1);                        // lowest one (first output, last tap)
+        if (lowest < 0) lowest = 0;
+        while (hi >= lowest) {
+            long long lo = hi - (RESAMPLE_WINDOW - 4);                               // window [lo, hi], lo a multiple of 4: at most WINDOW samples
+            if (lo < lowest) lo = lowest;
+            lo &= ~3ll;
+            const int n4 = (int)((hi - lo) / 4) + 1;
+            for (int i = t; i < n4; i += RESAMPLE_THREADS) {
+                const long long k = lo + 4ll * i;
+                float4 v;
+                if (vec && k + 3 < len) v = *reinterpret_cast<const float4*>(xr + k);
+                else v = make_float4(k < len ? xr[k] : 0.f, k + 1 < len ? xr[k + 1] : 0.f, k + 2 < len ? xr[k + 2] : 0.f, k + 3 < len ? xr[k + 3] : 0.f);
+                *reinterpret_cast<float4*>(xs + 4 * i) = v;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < RESAMPLE_PER_THREAD; ++j) {
+                long long m0 = q[j] - hi, m1 = q[j] - lo;                            // the taps whose sample q - m lies in [lo, hi]
+                if (m0 < 0) m0 = 0;
+                if (m1 > Mp[j] - 1) m1 = Mp[j] - 1;
+                if (m0 > m1) continue;
+                const int at = (int)(q[j] - lo);                                     // sample q - m sits at xs[at - m]: inside the window for m in [m0, m1]
+                float a = acc[j];
+                for (int m = (int)m0; m <= (int)m1; ++m) a = fmaf(tp[j][m], xs[at - m], a);
+                acc[j] = a;
+            }
+            __syncthreads();
+            hi = lo - 1;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < RESAMPLE_PER_THREAD; ++j) {
+        const long long n = n0 + j * RESAMPLE_THREADS + t;
+        if (n < L_out) yr[n] = acc[j];
+    }
+}
+
 }  // namespace storm
 
 using namespace storm;
@@ -190,6 +270,71 @@ extern "C" int storm_istft(const float* spec, const float* peak, float* wav, flo
     hipLaunchKernelGGL(istft_frames_kernel, dim3(T, B), dim3(256), 0, st, spec, frames, window, twiddle, T, n_fft, spec_factor, spec_abs_exponent);
     STORM_LAUNCH_CHECK();
     hipLaunchKernelGGL(istft_ola_kernel, dim3(cdiv(L, 256), B), dim3(256), 0, st, frames, window, peak, wav, T, L, stride, n_fft, hop, row_len);
+    STORM_LAUNCH_CHECK();
+    return STORM_OK;
+}
+
+// ---- resampling: filter design on the host (the single source of the coefficients) and the launch ----
+namespace {
+int resample_gcd(int a, int b) { while (b) { const int r = a % b; a = b; b = r; } return a; }
+// modified Bessel function I0 by its power series sum_k ((x/2)^k / k!)^2, to fp64 convergence
+double bessel_i0(double x) {
+    const double y = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 500; ++k) {
+        term *= y / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-17 * sum) break;
+    }
+    return sum;
+}
+}  // namespace
+
+extern "C" int storm_resample_num_taps(int up, int down) {
+    STORM_CHECK(up >= 1 && down >= 1, "storm_resample: up=%d down=%d (both must be >= 1)", up, down);
+    STORM_CHECK(resample_gcd(up, down) == 1, "storm_resample: ratio %d / %d is not reduced (gcd %d)", up, down, resample_gcd(up, down));
+    const int R = up > down ? up : down;
+    STORM_CHECK(R <= STORM_RESAMPLE_MAX_RATE, "storm_resample: max(up, down) = %d exceeds %d", R, STORM_RESAMPLE_MAX_RATE);
+    return 2 * 10 * R + 1;
+}
+
+extern "C" int storm_resample_taps(int up, int down, float* taps_phase_major, long long capacity) {
+    const int ntaps = storm_resample_num_taps(up, down);
+    if (ntaps < 0) return ntaps;
+    STORM_CHECK(taps_phase_major != nullptr, "storm_resample_taps: null pointer");
+    const int R = up > down ? up : down, half = 10 * R, M = (ntaps + up - 1) / up;
+    STORM_CHECK(capacity >= (long long)up * M, "storm_resample_taps: capacity %lld for a table of %d x %d", capacity, up, M);
+    // firwin(2 half + 1, 1 / R, window = ('kaiser', 5.0)) * up in fp64: sinc low-pass at 1 / R of Nyquist under a Kaiser window, unit DC gain
+    const double beta = 5.0, pi = 3.14159265358979323846, fc = 1.0 / (double)R, i0b = bessel_i0(beta);
+    double sum = 0.0;
+    const auto tap = [&](int j) {
+        const double n = (double)(j - half), r = n / (double)half, arg = pi * (fc * n);     // (fc n first: exact multiples of R land on exact integers)
+        const double w = bessel_i0(beta * sqrt(1.0 - r * r > 0.0 ? 1.0 - r * r : 0.0)) / i0b;
+        return fc * (j == half ? 1.0 : sin(arg) / arg) * w;
+    };
+    for (int j = 0; j < ntaps; ++j) sum += tap(j);
+    for (int p = 0; p < up; ++p)
+        for (int m = 0; m < M; ++m) {
+            const int j = p + m * up;
+            taps_phase_major[(long long)p * M + m] = j < ntaps ? (float)(tap(j) / sum * (double)up) : 0.f;       // rounded to fp32 once; zero past M_p
+        }
+    return STORM_OK;
+}
+
+extern "C" int storm_resample_poly(const float* x, float* y, const float* taps, int B, long long L_in, long long stride_in, long long L_out,
+                                   long long stride_out, const int* row_len, int up, int down, storm_stream_t s) {
+    STORM_CHECK(x && y && taps, "storm_resample_poly: null pointer (x=%p y=%p taps=%p)", (const void*)x, (const void*)y, (const void*)taps);
+    const int ntaps = storm_resample_num_taps(up, down);
+    if (ntaps < 0) return ntaps;
+    STORM_CHECK(B >= 1 && B <= 65535 && L_in >= 1 && L_in <= (1ll << 40), "storm_resample_poly: B=%d L_in=%lld", B, L_in);
+    STORM_CHECK(L_out == (L_in * up + down - 1) / down, "storm_resample_poly: L_out=%lld, %lld samples at %d / %d give %lld", L_out, L_in, up, down,
+                (L_in * up + down - 1) / down);
+    STORM_CHECK(stride_in >= L_in && stride_out >= L_out, "storm_resample_poly: stride_in=%lld stride_out=%lld for rows of %lld / %lld", stride_in,
+                stride_out, L_in, L_out);
+    const long long tiles = (L_out + RESAMPLE_TILE - 1) / RESAMPLE_TILE;
+    STORM_CHECK(tiles <= 0x7fffffffll, "storm_resample_poly: L_out=%lld", L_out);
+    hipLaunchKernelGGL(resample_poly_kernel, dim3((unsigned)tiles, B), dim3(RESAMPLE_THREADS), 0, (hipStream_t)s, x, y, taps, L_in, stride_in, L_out,
+                       stride_out, row_len, up, down, (ntaps - 1) / 2, (ntaps + up - 1) / up);
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }

@@ -16,6 +16,8 @@ def get_window(window_type, window_length):
 
 
 class SpecsDataModule:
+    sample_rate = 16000                  # the reference's model_sr (enhancement.py:69): the rate the networks were trained at
+
     def __init__(self, base_dir="", format="wsj0", spatial_channels=1, batch_size=8, n_fft=510, hop_length=128,
                  num_frames=256, window="hann", num_workers=8, dummy=False, spec_factor=0.15,
                  spec_abs_exponent=0.5, gpu=True, return_time=False, **kwargs):
@@ -58,6 +60,20 @@ class SpecsDataModule:
             length = self.hop_length * (X.shape[-1] - 1)
         w = ops.istft(X.contiguous(), int(length), None, n_fft=self.n_fft, hop=self.hop_length, window=self.window_type)
         return w[0] if squeeze else w
+
+    # ---- other sample rates (no counterpart upstream, which asserts 16 kHz input) -----------------
+    @staticmethod
+    def resample(wav, sr_in, sr_out, lengths=None):
+        """wav [B, L], [C, L] or [L] float32 at rate sr_in -> the same at sr_out, ceil(L sr_out / sr_in) samples per row
+        (ops.resample_poly: scipy.signal.resample_poly's default Kaiser filter).  lengths: per-row sample counts of a ragged
+        batch.  Equal rates return `wav` itself."""
+        up, down = ops.resample_ratio(sr_out, sr_in)
+        if up == down:
+            return wav
+        squeeze = wav.dim() == 1
+        x = wav.unsqueeze(0) if squeeze else wav
+        y = ops.resample_poly(x.float(), up, down, lengths=lengths)
+        return y[0] if squeeze else y
 
     # ---- fused batched forms used by enhance() ---------------------------------------------------
     def padded_frames(self, length, pad_to=64):

@@ -171,6 +171,34 @@ class _Base(nn.Module):
         Y, peak = self.data_module.wav_to_spec(yd, pad_to=64, lengths=lengths)
         return Y, peak, y.size(1)
 
+    # ---- audio at another rate than the model's (an extension: upstream asserts 16 kHz input, enhancement.py:69) -----------
+    def _off_rate(self, sr):
+        return sr is not None and int(sr) != self.data_module.sample_rate
+
+    def _to_model_rate(self, y, sr, lengths=None):
+        """y [B, L] at rate sr (lengths: the rows' own sample counts) -> (y resampled to the model rate on the device, the rows' counts there)"""
+        dm = self.data_module
+        if y.dim() != 2:
+            raise ValueError("expected a waveform batch [B, L]")
+        l16 = None
+        if lengths is not None:
+            lengths = [int(v) for v in lengths]
+            l16 = [-(-v * dm.sample_rate // int(sr)) for v in lengths]
+            tp = {dm.padded_frames(v) for v in l16}
+            if len(tp) != 1 or max(lengths) != y.shape[1]:
+                raise ValueError(f"a ragged batch must share one padded frame count at the model rate of {dm.sample_rate} Hz and be as wide as its longest "
+                                 f"row: the rows' {lengths} samples at {int(sr)} Hz are {l16} samples there, padded frame counts {sorted(tp)}")
+        return dm.resample(y.to(device=self.device, dtype=torch.float32), int(sr), dm.sample_rate, lengths=lengths), l16
+
+    def _from_model_rate(self, x16, sr, l16, lengths, width):
+        """the enhanced batch back at rate sr, every row trimmed to its input sample count (a round trip never comes back shorter:
+        ceil(ceil(L u / d) d / u) >= L) and zero past it"""
+        x = self.data_module.resample(x16, self.data_module.sample_rate, int(sr), lengths=l16)[:, :width].contiguous()
+        if lengths is not None:
+            for b, n in enumerate(lengths):
+                x[b, int(n):] = 0
+        return x
+
     # ---- validation loss: the reference's `_step` (model.py:138-154, 345-349, 560-595) ------------
     def _loss_draws(self, B, t, z, seed, row_seeds):
         """(t fp32 [B] on the host, noise keywords of the perturbation and the loss kernel).  t = t_eps + (T - t_eps) u (model.py:144)
@@ -309,7 +337,7 @@ class ScoreModel(_Base):
         return self._sampler_minibatched(lambda sl: sampling.get_ode_sampler(sde, self, y=y[sl], **self._slice_keys(kwargs, sl)), y, minibatch)
 
     def enhance_batch(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", N=50,
-                      corrector_steps=1, snr=0.5, return_nfe=False, lengths=None, row_seeds=None, **kwargs):
+                      corrector_steps=1, snr=0.5, return_nfe=False, lengths=None, row_seeds=None, sr=None, **kwargs):
         """B equal-length utterances y [B, L] in one sampler run.  Every op on the path is per utterance, the Langevin
         corrector runs with per-row step sizes and the ODE sampler with one Runge-Kutta step controller per row (the
         reference solves one utterance per solve_ivp call), so with INJECTED noise (noise_fn) row b equals enhance(y[b:b+1])
@@ -320,7 +348,16 @@ class ScoreModel(_Base):
         rounding, and bit for bit in every precision under storm_amd.set_batch_invariant().
         For sampler_type="ode" the returned nfe is the number of score evaluations executed (= the slowest row's count).
         lengths: ragged micro-batch - rows of different sample counts that share one padded frame count
-        (storm_amd.distributed.bucket_by_frames); y is zero filled to the longest row and so is the result."""
+        (storm_amd.distributed.bucket_by_frames); y is zero filled to the longest row and so is the result.
+        sr: the sample rate of y (and of lengths) when it is not the model's 16 kHz - y is resampled to 16 kHz on the device, enhanced as
+        a 16 kHz batch, resampled back and every row trimmed to its input sample count; the padded-frame rule of a ragged batch then
+        holds for the 16 kHz lengths."""
+        if self._off_rate(sr):
+            y16, l16 = self._to_model_rate(y, sr, lengths)
+            x16, nfe = self.enhance_batch(y16, sampler_type, predictor, corrector, N, corrector_steps, snr, return_nfe=True, lengths=l16,
+                                          row_seeds=row_seeds, **kwargs)
+            x_hat = self._from_model_rate(x16, sr, l16, lengths, y.shape[1])
+            return (x_hat, nfe) if return_nfe else x_hat
         Y, peak, T_orig = self._prepare(y, lengths)
         if row_seeds is not None:
             kwargs["row_seeds"] = row_seeds
@@ -358,9 +395,15 @@ class ScoreModel(_Base):
         return torch.mean(rows) if reduce else rows
 
     def enhance(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", N=50, corrector_steps=1,
-                snr=0.5, timeit=False, scale_factor=None, return_stft=False, **kwargs):
-        """One-call enhancement of one utterance y [1, L] (model.py:273-310)."""
+                snr=0.5, timeit=False, scale_factor=None, return_stft=False, sr=None, **kwargs):
+        """One-call enhancement of one utterance y [1, L] (model.py:273-310).  sr: y's sample rate when it is not 16 kHz (enhance_batch);
+        return_stft=True returns the 16 kHz spectrograms."""
         start = time.time()
+        if self._off_rate(sr):
+            if return_stft:
+                y, sr = self._to_model_rate(y, sr)[0], None
+            else:
+                kwargs["sr"] = sr
         if return_stft:
             Y, peak, T_orig = self._prepare(y)
             sampler = self.get_pc_sampler(predictor, corrector, Y, N=N, corrector_steps=corrector_steps, snr=snr, **kwargs)
@@ -371,7 +414,7 @@ class ScoreModel(_Base):
         x_hat = x_hat.squeeze().cpu()
         end = time.time()
         if timeit:
-            rtf = (end - start) / (len(x_hat) / 16000)
+            rtf = (end - start) / (len(x_hat) / (sr or 16000))
             return x_hat, nfe, rtf
         return x_hat
 
@@ -417,7 +460,12 @@ class DiscriminativeModel(ScoreModel):
                 rows = ops.pair_loss_rows(x, x_hat, kind=self.loss_type, frames=frames)
         return torch.mean(rows) if reduce else rows
 
-    def enhance(self, y, **ignored_kwargs):
+    def enhance(self, y, sr=None, **ignored_kwargs):
+        """sr: y's sample rate when it is not 16 kHz - resampled on the device before and after, as in ScoreModel.enhance_batch"""
+        if self._off_rate(sr):
+            y16, _ = self._to_model_rate(y, sr)
+            x16 = self.enhance(y16).reshape(y16.shape[0], -1)
+            return self._from_model_rate(x16, sr, None, None, y.shape[1]).squeeze()
         with torch.no_grad():
             Y, peak, T_orig = self._prepare(y)
             X_hat = self(Y)
@@ -510,8 +558,17 @@ class StochasticRegenerationModel(_Base):
 
     def enhance_batch(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="none", N=30,
                       corrector_steps=1, snr=0.5, denoiser_only=False, return_nfe=False, return_stft=False, lengths=None,
-                      row_seeds=None, **kwargs):
-        """row_seeds: one Philox key per row, as in ScoreModel.enhance_batch (row b draws what its batch-1 run with seed = s_b draws)"""
+                      row_seeds=None, sr=None, **kwargs):
+        """row_seeds: one Philox key per row, as in ScoreModel.enhance_batch (row b draws what its batch-1 run with seed = s_b draws);
+        sr: the sample rate of y and lengths when it is not 16 kHz, as there (return_stft=True returns the 16 kHz spectrograms)"""
+        if self._off_rate(sr):
+            y16, l16 = self._to_model_rate(y, sr, lengths)
+            out = self.enhance_batch(y16, sampler_type, predictor, corrector, N, corrector_steps, snr, denoiser_only=denoiser_only,
+                                     return_nfe=True, return_stft=return_stft, lengths=l16, row_seeds=row_seeds, **kwargs)
+            if return_stft:
+                return out
+            x_hat = self._from_model_rate(out[0], sr, l16, lengths, y.shape[1])
+            return (x_hat, out[1]) if return_nfe else x_hat
         Y, peak, T_orig = self._prepare(y, lengths)
         kwargs.setdefault("langevin_per_row", True)
         if row_seeds is not None:
@@ -536,9 +593,12 @@ class StochasticRegenerationModel(_Base):
         return (x_hat, nfe) if return_nfe else x_hat
 
     def enhance(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="none", N=30, corrector_steps=1,
-                snr=0.5, timeit=False, scale_factor=None, return_stft=False, denoiser_only=False, **kwargs):
-        """model.py:720-780; return_stft=True returns (sample, Y, T_orig, norm_factor) like the reference."""
+                snr=0.5, timeit=False, scale_factor=None, return_stft=False, denoiser_only=False, sr=None, **kwargs):
+        """model.py:720-780; return_stft=True returns (sample, Y, T_orig, norm_factor) like the reference.  sr: y's sample rate when it is
+        not 16 kHz (enhance_batch)."""
         start = time.time()
+        if self._off_rate(sr):
+            kwargs["sr"] = sr
         out = self.enhance_batch(y, sampler_type, predictor, corrector, N, corrector_steps, snr,
                                  denoiser_only=denoiser_only, return_nfe=True, return_stft=return_stft, **kwargs)
         if return_stft:
@@ -547,5 +607,5 @@ class StochasticRegenerationModel(_Base):
         x_hat = x_hat.squeeze().cpu()
         end = time.time()
         if timeit:
-            return x_hat, nfe, (end - start) / (len(x_hat) / 16000)
+            return x_hat, nfe, (end - start) / (len(x_hat) / (sr or 16000))
         return x_hat

@@ -721,6 +721,71 @@ def istft(spec, length, peak=None, n_fft=510, hop=128, spec_factor=1.0, spec_abs
     return wav
 
 
+# ---------------------------------------------------------------- resampling --------------
+RESAMPLE_TILE = L.RESAMPLE_TILE          # outputs per workgroup of storm_resample_poly (tests place lengths around it)
+_resample_tables = {}
+
+
+def resample_ratio(up, down):
+    """(up, down) reduced by their gcd; the library refuses what is left if it is out of its range"""
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError(f"resample: up={up} down={down} (both must be >= 1)")
+    g = math.gcd(up, down)
+    return up // g, down // g
+
+
+def resample_length(n, up, down):
+    """samples of an n-sample signal after resampling by up / down: ceil(n up / down)"""
+    up, down = resample_ratio(up, down)
+    return -(-int(n) * up // down)
+
+
+def _resample_table(up, down, device):
+    """the phase-major tap table [up, M] of the reduced ratio on `device`: designed by the library (storm_resample_taps), fetched once"""
+    key = (up, down, str(device))
+    if key not in _resample_tables:
+        n = L.lib().storm_resample_num_taps(up, down)
+        if n < 0:
+            L.check(n, "storm_resample_num_taps")
+        M = -(-n // up)
+        host = torch.empty((up, M), dtype=torch.float32)
+        L.check(L.lib().storm_resample_taps(up, down, host.data_ptr(), host.numel()), "storm_resample_taps")
+        _resample_tables[key] = host.to(device)
+    return _resample_tables[key]
+
+
+def resample_taps(up, down, device="cpu"):
+    """The library's filter for the ratio up / down as its kernel reads it: fp32 [up, M], T[p][m] = h[p + m up], zero past the phase's
+    last tap (include/storm_hip.h: storm_resample_taps).  A copy: the cached table stays as the library wrote it."""
+    up, down = resample_ratio(up, down)
+    return _resample_table(up, down, torch.device(device)).clone()
+
+
+def resample_poly(x, up, down, lengths=None):
+    """x [B, L] fp32 (row stride may exceed L) -> [B, ceil(L up / down)]: scipy.signal.resample_poly(x, up, down) with its defaults,
+    every output one fp32 FMA chain.  lengths: per-row sample counts of a ragged batch - row b gets ceil(lengths[b] up / down)
+    outputs and zeros after them; its samples past lengths[b] are not read.  A ratio of 1 returns x itself (no launch)."""
+    up, down = resample_ratio(up, down)
+    if up == down:
+        return x
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"resample_poly: expected a float32 batch [B, L], got {x.dtype} {tuple(x.shape)}")
+    B, Lin = x.shape
+    if lengths is not None and (len(lengths) != B or int(max(int(v) for v in lengths)) > Lin):
+        raise ValueError(f"resample_poly: lengths {[int(v) for v in lengths]} for a batch {tuple(x.shape)}")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    Lout = -(-Lin * up // down)
+    taps = _resample_table(up, down, x.device)
+    y = torch.empty((B, Lout), dtype=torch.float32, device=x.device)
+    rl = _row_len(lengths, x)
+    stride = x.stride(0) if B > 1 else Lin                       # (a one-row tensor's row stride is whatever its producer left there)
+    L.check(L.lib().storm_resample_poly(L.ptr_rows(x), L.ptr(y), L.ptr(taps), B, Lin, stride, Lout, y.stride(0), L.ptr(rl), up, down,
+                                        L.stream()), "storm_resample_poly")
+    return y
+
+
 # ---------------------------------------------------------------- ConvTasNet --------------
 TASNET_ENCODE, TASNET_POINTWISE, TASNET_DEPTHWISE = 0, 1, 2
 
