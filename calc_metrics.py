@@ -1,0 +1,88 @@
+#!/usr/bin/env python
+"""Score a directory of enhanced files against the clean and noisy ones - the reference's calc_metrics step on the device:
+
+    python calc_metrics.py --clean_dir clean/ --noisy_dir noisy/ --enhanced_dir out/ [--batch 16] [--resample]
+
+Files are matched by basename (every *.wav of --enhanced_dir needs its clean and noisy namesake).  Each triple is trimmed to its
+shortest member, the triples are bucketed by frame count and scored as ragged micro-batches (storm_amd.util.inference.score_batch:
+SI-SDR / SI-SIR / SI-SAR, LSD and the input SNR, util/other.py:16-44, 96-100); PESQ and ESTOI are added on the host when the `pesq`
+/ `pystoi` packages import.  Written into --enhanced_dir:
+
+    _results.csv       Filename,Length,iSNR,si_sdr,si_sir,si_sar,lsd[,pesq,estoi] - one line per file, Length in samples at 16 kHz
+    _avg_results.txt   metric: mean ± std of each column (mean_std, NaNs dropped)
+
+A file's line does not depend on --batch nor on the other files.  --resample: files of other rates are resampled to 16 kHz on the
+device when they are loaded (SpecsDataModule.resample); without it such a file is refused, as in enhancement.py."""
+import glob
+import os
+from argparse import ArgumentParser
+
+import numpy as np
+import torch
+
+from enhancement import read_wav
+
+SR = 16000
+COLUMNS = ("iSNR", "si_sdr", "si_sir", "si_sar", "lsd")
+KEYS = {"iSNR": "isnr", "si_sdr": "si_sdr", "si_sir": "si_sir", "si_sar": "si_sar", "lsd": "lsd"}
+
+
+def main():
+    p = ArgumentParser()
+    p.add_argument("--clean_dir", type=str, required=True, help="Directory of the clean files.")
+    p.add_argument("--noisy_dir", type=str, required=True, help="Directory of the noisy files.")
+    p.add_argument("--enhanced_dir", type=str, required=True, help="Directory of the enhanced files; the results are written here.")
+    p.add_argument("--batch", type=int, default=16, help="files per scoring micro-batch")
+    p.add_argument("--resample", action="store_true", help="read files of any sample rate: each is resampled to 16 kHz on the device when it is loaded")
+    args = p.parse_args()
+
+    from storm_amd import distributed as D
+    from storm_amd.data_module import SpecsDataModule
+    from storm_amd.util.inference import _optional, score_batch
+    from storm_amd.util.other import mean_std
+    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+
+    def load(path):
+        x, sr = read_wav(path)
+        if not args.resample:
+            assert sr == SR, "You need to make sure sample_sr matches model_sr --> resample to 16kHz"
+        return SpecsDataModule.resample(x[0].to(dev), sr, SR)                  # first channel
+
+    names = [os.path.basename(f) for f in sorted(glob.glob(os.path.join(args.enhanced_dir, "*.wav")))]
+    triples = []
+    for name in names:
+        x, y, e = (load(os.path.join(d, name)) for d in (args.clean_dir, args.noisy_dir, args.enhanced_dir))
+        n = min(x.shape[0], y.shape[0], e.shape[0])
+        triples.append((x[:n], y[:n], e[:n]))
+    lengths = [t[0].shape[0] for t in triples]
+    values = {c: [None] * len(names) for c in COLUMNS}
+    for ids in D.bucket_by_frames(lengths, args.batch):
+        lens = [lengths[i] for i in ids]
+        rows = torch.zeros(3, len(ids), max(lens), device=dev)
+        for k, i in enumerate(ids):
+            for j in range(3):
+                rows[j, k, :lens[k]] = triples[i][j]
+        scores = {k: v.cpu() for k, v in score_batch(rows[0], rows[1], rows[2], lengths=lens).items()}
+        for k, i in enumerate(ids):
+            for c in COLUMNS:
+                values[c][i] = float(scores[KEYS[c]][k])
+    columns = list(COLUMNS)
+    pesq, stoi = _optional("pesq", "pesq"), _optional("pystoi", "stoi")
+    if pesq is not None and stoi is not None:
+        columns += ["pesq", "estoi"]
+        values["pesq"] = [pesq(SR, x.cpu().numpy(), e.cpu().numpy(), "wb") for x, _, e in triples]
+        values["estoi"] = [stoi(x.cpu().numpy(), e.cpu().numpy(), SR, extended=True) for x, _, e in triples]
+
+    table = [[f"{values[c][i]:.6f}" for c in columns] for i in range(len(names))]
+    with open(os.path.join(args.enhanced_dir, "_results.csv"), "w", encoding="utf-8") as f:
+        f.write(",".join(["Filename", "Length"] + columns) + "\n")
+        for i, name in enumerate(names):
+            f.write(",".join([name, str(lengths[i])] + table[i]) + "\n")
+    with open(os.path.join(args.enhanced_dir, "_avg_results.txt"), "w", encoding="utf-8") as f:
+        for j, c in enumerate(columns):                                        # (of the printed values: the averages follow from _results.csv alone)
+            mean, std = mean_std(np.array([float(row[j]) for row in table]))
+            f.write(f"{c}: {mean:.6f} ± {std:.6f}\n")
+
+
+if __name__ == "__main__":
+    main()

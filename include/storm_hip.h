@@ -488,6 +488,30 @@ int storm_resample_poly(const float* x, float* y, const float* taps, int B, long
                         long long L_out, long long stride_out, const int* row_len, int up, int down, storm_stream_t s);
 
 /* ------------------------------------------------------------------------------------------
+ * Metrics of enhanced audio (the reference's calc_metrics step; definitions in util/other.py).  Both are one streaming pass: a row is cut
+ * at FIXED positions, a workgroup sums one piece in fp64 into the caller's scratch, a second kernel adds a row's pieces in index order -
+ * no atomics, and a row's numbers are the same bits at any B, batch width, row stride and position in the batch.
+ *
+ * storm_energy_ratios_rows: s_hat, s, n fp32 [B][L] (row strides in floats) -> out fp64 [B][4] =
+ *   (SI-SDR, SI-SIR, SI-SAR) = energy_ratios(s_hat, s, n) (util/other.py:35-44) on the decomposition of si_sdr_components (:21-33), whose
+ *   eps is always its own default 1e-10 (energy_ratios does not pass its argument on), and the input SNR snr_dB(s, n) (:96-100).
+ *   From the six inner products of (s_hat, s, n), accumulated in fp64 (fp32 x fp32 is exact there) over pieces of STORM_METRICS_CHUNK
+ *   samples; |s_hat - alpha_s s|^2 and |s_hat - alpha_s s - alpha_n n|^2 are expanded in them.  row_len (optional, device int32 [B]):
+ *   row b is its first row_len[b] samples; the rest is never read.
+ * storm_lsd_rows: two complex64 spectrograms [B][F][T] (storm_stft's layout) -> out fp64 [B] =
+ *   sqrt(mean_{f, t < frames_b} |2 ln(eps + |spec_hat|) - 2 ln(eps + |spec|)|), lsd of util/other.py:16-19 after its two STFTs (one mean
+ *   over all bins, then the root); magnitudes and logarithms in fp64.  row_frames (optional, device int32 [B]): the rows' own frame counts
+ *   (padding frames are not counted).
+ * scratch: device memory of at least the _scratch_bytes of the same (B, L) / (B, F, T), 8-byte aligned, pure scratch. */
+#define STORM_METRICS_CHUNK 16384
+long long storm_energy_ratios_scratch_bytes(int B, long long L);
+int storm_energy_ratios_rows(const float* s_hat, const float* s, const float* n, double* out, void* scratch, long long scratch_bytes, int B,
+                             long long L, long long stride_hat, long long stride_s, long long stride_n, const int* row_len, storm_stream_t st);
+long long storm_lsd_scratch_bytes(int B, int F, int T);
+int storm_lsd_rows(const float* spec_hat, const float* spec, double* out, void* scratch, long long scratch_bytes, int B, int F, int T,
+                   const int* row_frames, double eps, storm_stream_t st);
+
+/* ------------------------------------------------------------------------------------------
  * ConvTasNet (backbones/convtasnet.py): the time-domain denoiser.  Activations are channels-last [B][L][C] in `dtype`
  * (C % 8 == 0); the TCN's running sums `output` / `skip_connection` are fp32 [B][L][BN]; statistics are fp32.  A global layer
  * norm (GroupNorm(1, C, eps) over all of C x L of a row) is never materialised: the producing kernel writes per-wave

@@ -338,3 +338,6 @@ extern "C" int storm_resample_poly(const float* x, float* y, const float* taps, 
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }
+
+// ---- evaluation metrics of enhanced audio (storm_energy_ratios_rows, storm_lsd_rows): kernels and entry points ----
+#include "metrics.h"

@@ -786,6 +786,58 @@ def resample_poly(x, up, down, lengths=None):
     return y
 
 
+# ---------------------------------------------------------------- metrics -----------------
+METRICS_CHUNK = L.METRICS_CHUNK          # samples per workgroup of storm_energy_ratios_rows (tests place lengths around it)
+
+
+def _metric_lengths(who, lengths, B, width, what):
+    """lengths of a ragged batch checked on the host: one per row, each in [1, width]"""
+    if lengths is None:
+        return
+    vals = [int(v) for v in lengths]
+    if len(vals) != B or min(vals) < 1 or max(vals) > width:
+        raise ValueError(f"{who}: {what} {vals} for a batch of {B} rows x {width}")
+
+
+def energy_ratios_rows(s_hat, s, n, lengths=None):
+    """fp64 [B, 4] = (SI-SDR, SI-SIR, SI-SAR, input SNR) in dB per row of three fp32 waveform batches [B, L] (rows may be strided views):
+    energy_ratios(s_hat, s, n) and snr_dB(s, n) of util/other.py:21-44, 96-100.  lengths: per-row sample counts of a ragged batch (the
+    rest of a row is not read).  A row's numbers do not depend on the batch it is in."""
+    for name, x in (("s_hat", s_hat), ("s", s), ("n", n)):
+        if x.dim() != 2 or x.dtype != torch.float32 or x.shape != s_hat.shape:
+            raise ValueError(f"energy_ratios_rows: {name} is {x.dtype} {tuple(x.shape)}, expected float32 [B, L] = {tuple(s_hat.shape)}")
+    B, Lw = s_hat.shape
+    if B < 1 or Lw < 1:
+        raise ValueError(f"energy_ratios_rows: empty batch {tuple(s_hat.shape)}")
+    _metric_lengths("energy_ratios_rows", lengths, B, Lw, "lengths")
+    rows = [x if x.stride(1) == 1 else x.contiguous() for x in (s_hat, s, n)]
+    strides = [x.stride(0) if B > 1 else Lw for x in rows]       # (a one-row tensor's row stride is whatever its producer left there)
+    out = _alloc((B, 4), torch.float64, s_hat)
+    ws = torch.empty((L.lib().storm_energy_ratios_scratch_bytes(B, Lw),), dtype=torch.uint8, device=s_hat.device)
+    rl = _row_len(lengths, s_hat)
+    L.check(L.lib().storm_energy_ratios_rows(L.ptr_rows(rows[0]), L.ptr_rows(rows[1]), L.ptr_rows(rows[2]), L.ptr(out), L.ptr(ws), ws.numel(),
+                                             B, Lw, strides[0], strides[1], strides[2], L.ptr(rl), L.stream()), "storm_energy_ratios_rows")
+    return out
+
+
+def lsd_rows(S_hat, S, frames=None, eps=1e-10):
+    """fp64 [B]: the log-spectral distance sqrt(mean |2 ln(eps + |S_hat|) - 2 ln(eps + |S|)|) per row of two complex64 spectrogram batches
+    [B, F, T] (util/other.py:16-19 after its STFTs).  frames: per-row valid frame counts (the padding frames of a row stay out)."""
+    if S_hat.shape != S.shape or S_hat.dim() != 3 or S_hat.dtype != torch.complex64 or S.dtype != torch.complex64:
+        raise ValueError(f"lsd_rows: {S_hat.dtype} {tuple(S_hat.shape)} against {S.dtype} {tuple(S.shape)}, expected two complex64 [B, F, T]")
+    B, F, T = S_hat.shape
+    if min(B, F, T) < 1:
+        raise ValueError(f"lsd_rows: empty batch {tuple(S_hat.shape)}")
+    _metric_lengths("lsd_rows", frames, B, T, "frames")
+    S_hat, S = S_hat.contiguous(), S.contiguous()
+    out = _alloc((B,), torch.float64, S_hat)
+    ws = torch.empty((L.lib().storm_lsd_scratch_bytes(B, F, T),), dtype=torch.uint8, device=S_hat.device)
+    rf = _row_len(frames, S_hat)
+    L.check(L.lib().storm_lsd_rows(L.ptr(_r(S_hat)), L.ptr(_r(S)), L.ptr(out), L.ptr(ws), ws.numel(), B, F, T, L.ptr(rf), float(eps), L.stream()),
+            "storm_lsd_rows")
+    return out
+
+
 # ---------------------------------------------------------------- ConvTasNet --------------
 TASNET_ENCODE, TASNET_POINTWISE, TASNET_DEPTHWISE = 0, 1, 2
 

@@ -15,7 +15,7 @@ import math
 import torch
 
 from ..distributed import bucket_by_frames
-from .other import si_sdr_batch
+from .other import lsd, si_sdr_batch
 
 # Settings of the reference's validation runs (util/inference.py:11-13)
 snr = 0.5
@@ -31,12 +31,27 @@ def _optional(name, attr):
         return None
 
 
+METRIC_KEYS = ("si_sdr", "si_sir", "si_sar", "lsd", "isnr")
+
+
+def score_batch(clean, noisy, estimate, lengths=None):
+    """The calc_metrics numbers of one micro-batch of device waveforms [B, L]: a dict of fp64 [B] tensors si_sdr / si_sir / si_sar
+    (energy_ratios(estimate, clean, noisy - clean), util/other.py:35-44), lsd (estimate against clean, :16-19) and isnr (snr_dB(clean,
+    noisy - clean), :96-100).  lengths: per-row sample counts of a ragged batch.  One energy launch pair, two STFTs and one LSD launch
+    pair; every row's numbers are those of its own one-row call."""
+    from .. import ops
+    clean, noisy, estimate = clean.float(), noisy.float(), estimate.float()
+    r = ops.energy_ratios_rows(estimate, clean, noisy - clean, lengths=lengths)
+    return {"si_sdr": r[:, 0], "si_sir": r[:, 1], "si_sar": r[:, 2], "lsd": lsd(estimate, clean, lengths=lengths), "isnr": r[:, 3]}
+
+
 def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminative=False, pairs=None, batch=16, noise_for=None,
-                   **enhance_kwargs):
+                   metrics=False, **enhance_kwargs):
     """Returns (pesq, si_sdr, estoi, [noisy, estimate, clean spectrograms] | None, [noisy, estimate, clean audio] | None),
     the reference's tuple.  `discriminative` is accepted for signature parity (the model class decides the path).
     noise_for(ids) -> noise_fn: injected sampler noise for the micro-batch of files `ids` (parity tests; production runs
-    pass seed= and draw in-kernel)."""
+    pass seed= and draw in-kernel).  metrics=True appends a sixth element: the means over the evaluated files of score_batch's
+    numbers, {si_sdr, si_sir, si_sar, lsd, isnr} as floats, computed on the same micro-batches."""
     model.eval()
     pesq, stoi = _optional("pesq", "pesq"), _optional("pystoi", "stoi")
     if pairs is None:
@@ -47,6 +62,7 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
     dev = next(model.parameters()).device
     est = [None] * n
     sdr = torch.zeros(n, dtype=torch.float64)
+    scores = {k: torch.zeros(n, dtype=torch.float64) for k in METRIC_KEYS} if metrics else None
     hop = model.data_module.hop_length
     batched = hasattr(model, "enhance_batch") and not discriminative
     for ids in bucket_by_frames([p[1].shape[-1] for p in pairs], batch if batched else 1, hop=hop):
@@ -71,6 +87,10 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
         else:                                                               # ragged rows: every file over its own length
             for k, i in enumerate(ids):
                 sdr[i] = float(si_sdr_batch(x[k:k + 1, :lens[k]], x_hat[k:k + 1, :lens[k]]))
+        if metrics:
+            w = min(width, x_hat.shape[1])
+            for key, v in score_batch(x[:, :w], y[:, :w], x_hat[:, :w], lengths=[min(v, w) for v in lens]).items():
+                scores[key][ids] = v.cpu()
         for k, i in enumerate(ids):
             est[i] = x_hat[k, :lens[k]].cpu()
     _pesq = _estoi = float("nan")
@@ -86,7 +106,10 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
     if audio:
         k = min(n, MAX_VIS_SAMPLES)
         audios = [[pairs[i][1][0] for i in range(k)], [est[i] for i in range(k)], [pairs[i][0][0] for i in range(k)]]
-    return _pesq, float(sdr.mean()) if n else math.nan, _estoi, specs, audios
+    out = (_pesq, float(sdr.mean()) if n else math.nan, _estoi, specs, audios)
+    if metrics:
+        out += ({k: float(v.mean()) if n else math.nan for k, v in scores.items()},)
+    return out
 
 
 def validation_epoch(model, batches, seed=None, row_seeds=None, **loss_kwargs):

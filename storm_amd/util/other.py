@@ -1,5 +1,6 @@
 """Small utilities of sgmse/util/other.py that the hot path and the evaluation loop use:
-pad_spec (:102-109), si_sdr / si_sdr_torch (:82-94)."""
+pad_spec (:102-109), si_sdr / si_sdr_torch (:82-94), and the metrics of the calc_metrics step in batch form on the device:
+energy_ratios (:21-44), lsd (:16-19), snr_dB (:96-100); mean_std (:53-57) on the host."""
 import numpy as np
 import torch
 
@@ -32,3 +33,47 @@ def si_sdr_batch(s, s_hat, eps=0.0):
     """[B, L] device tensors -> [B] dB (one launch for the whole evaluation batch)"""
     from .. import ops
     return ops.si_sdr(s.float(), s_hat.float(), eps=eps)
+
+
+def _rows(x):
+    """a waveform or a batch of waveforms as a float32 batch [B, L]"""
+    x = x.float()
+    return x.reshape(1, -1) if x.dim() == 1 else x
+
+
+def energy_ratios(s_hat, s, n, lengths=None):
+    """(si_sdr, si_sir, si_sar) in dB, fp64 [B]: util/other.py:35-44 for every row of the device batches [B, L] (1-D tensors: one row);
+    eps = 1e-10 as si_sdr_components places it.  lengths: per-row sample counts of a ragged batch.  One kernel pair for the batch
+    (storm_energy_ratios_rows); a row's numbers do not depend on the batch it is in."""
+    from .. import ops
+    r = ops.energy_ratios_rows(_rows(s_hat), _rows(s), _rows(n), lengths=lengths)
+    return r[:, 0], r[:, 1], r[:, 2]
+
+
+def snr_dB(s, n, lengths=None):
+    """10 log10(mean s^2 / mean n^2) per row, fp64 [B] (util/other.py:96-100)"""
+    from .. import ops
+    s = _rows(s)
+    return ops.energy_ratios_rows(s, s, _rows(n), lengths=lengths)[:, 3]
+
+
+def lsd(s_hat, s, lengths=None, eps=1e-10):
+    """log-spectral distance per row of two waveform batches [B, L], fp64 [B] (util/other.py:16-19): the two STFTs (n_fft = 510, hop = 128,
+    periodic Hann, as stft_kwargs :14) are the engine's own, then storm_lsd_rows.  lengths: per-row sample counts; row b counts its own
+    1 + lengths[b] // 128 frames.  A row of <= 255 samples is refused by the STFT (reflect padding), as torch.stft refuses it."""
+    from .. import ops
+    s_hat, s = _rows(s_hat).contiguous(), _rows(s).contiguous()
+    if s_hat.shape != s.shape:
+        raise ValueError(f"lsd: {tuple(s_hat.shape)} against {tuple(s.shape)}")
+    if lengths is not None and len(lengths) != s.shape[0]:
+        raise ValueError(f"lsd: {len(lengths)} lengths for a batch of {s.shape[0]} rows")
+    S_hat, S = ops.stft(s_hat, lengths=lengths), ops.stft(s, lengths=lengths)
+    frames = None if lengths is None else [1 + int(v) // 128 for v in lengths]
+    return ops.lsd_rows(S_hat, S, frames=frames, eps=eps)
+
+
+def mean_std(data):
+    """(mean, population std) of the values that are not NaN (util/other.py:53-57); host"""
+    data = np.asarray(data.detach().cpu() if isinstance(data, torch.Tensor) else data, dtype=np.float64)
+    data = data[~np.isnan(data)]
+    return np.mean(data), np.std(data)
