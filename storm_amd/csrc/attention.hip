@@ -467,7 +467,20 @@ static int attn_group_launch(const AttnProblem* dev_tab, const AttnItem* dev_ite
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }
-int attn_query_blocks(int L) { return cdiv(L, BQ); }
+bool attn_group_supported(int C, int dtype) { return (dtype == STORM_BF16 || dtype == STORM_F16) && storm_attention_supported(C, dtype); }
+long long attn_group_table_bytes(int P) { return ((long long)P * (long long)sizeof(AttnProblem) + 255) / 256 * 256; }
+long long attn_group_items(int B, int L) { return (long long)B * cdiv(L, BQ); }
+long long attn_group_problem(int g, const void* q, const void* k, const void* vT, void* out, int B, int L, int C, int ldv, AttnProblem& t, AttnItem* items) {
+    memset(&t, 0, sizeof(t));
+    t.q = q; t.k = k; t.vT = vT; t.out = out; t.L = L; t.ldv = ldv;
+    t.q_bs = (long long)L * C; t.k_bs = (long long)L * C; t.v_bs = (long long)C * ldv; t.o_bs = (long long)L * C;
+    // long rows first inside the list would balance better; the order is the problems' (deterministic, the result does not depend on it)
+    long long n = 0;
+    const int nq = cdiv(L, BQ);
+    for (int b = 0; b < B; ++b)
+        for (int qb = 0; qb < nq; ++qb) { AttnItem& a = items[n++]; a.problem = g; a.b = b; a.qblock = qb; a.pad_ = 0; }
+    return n;
+}
 int launch_attention_group(const AttnProblem* dev_tab, const AttnItem* dev_items, int n_items, const float* bias, int C, float scale, int dtype, hipStream_t st) {
     STORM_CHECK(dev_tab && dev_items && n_items > 0 && (dtype == STORM_BF16 || dtype == STORM_F16) && (C == 32 || C == 64 || C == 128 || C == 256),
                 "storm_attention (group): bad arguments");
@@ -517,32 +530,28 @@ extern "C" int storm_attention(const void* q, const void* k, const void* vT, con
 extern "C" long long storm_attention_group_blob_bytes(const int* B, const int* L, int P) {
     if (B == nullptr || L == nullptr || P < 1) return -1;
     long long items = 0;
-    for (int g = 0; g < P; ++g) items += (long long)B[g] * storm::attn_query_blocks(L[g]);
-    return ((long long)P * (long long)sizeof(storm::AttnProblem) + 255) / 256 * 256 + items * (long long)sizeof(storm::AttnItem);
+    for (int g = 0; g < P; ++g) items += storm::attn_group_items(B[g], L[g]);
+    return storm::attn_group_table_bytes(P) + items * (long long)sizeof(storm::AttnItem);
 }
 extern "C" int storm_attention_group(const void* const* q, const void* const* k, const void* const* vT, void* const* out, const int* B, const int* L,
                                      const int* ldv, int P, const float* bias, int C, float scale, int dtype, void* blob, long long blob_bytes,
                                      storm_stream_t s) {
     using namespace storm;
     STORM_CHECK(q && k && vT && out && B && L && ldv && P >= 1 && blob, "storm_attention_group: bad arguments");
-    if ((dtype != STORM_BF16 && dtype != STORM_F16) || !storm_attention_supported(C, dtype)) {
+    if (!attn_group_supported(C, dtype)) {
         set_error("storm_attention_group: C=%d dtype=%d is outside the grouped kernel (16-bit operands, C in {32, 64, 128, 256})", C, dtype);
         return STORM_ERR_UNSUPPORTED;
     }
     const long long need = storm_attention_group_blob_bytes(B, L, P);
     STORM_CHECK(blob_bytes >= need, "storm_attention_group: blob %lld < %lld bytes", blob_bytes, need);
-    const long long tab = ((long long)P * (long long)sizeof(AttnProblem) + 255) / 256 * 256;
+    const long long tab = attn_group_table_bytes(P);
     std::vector<char> host((size_t)need);
     AttnProblem* t = reinterpret_cast<AttnProblem*>(host.data());
     AttnItem* it = reinterpret_cast<AttnItem*>(host.data() + tab);
     long long ni = 0;
     for (int g = 0; g < P; ++g) {
         STORM_CHECK(q[g] && k[g] && vT[g] && out[g] && B[g] > 0 && L[g] > 0 && ldv[g] >= L[g] && ldv[g] % 8 == 0, "storm_attention_group: problem %d", g);
-        memset(&t[g], 0, sizeof(AttnProblem));
-        t[g].q = q[g]; t[g].k = k[g]; t[g].vT = vT[g]; t[g].out = out[g]; t[g].L = L[g]; t[g].ldv = ldv[g];
-        t[g].q_bs = (long long)L[g] * C; t[g].k_bs = (long long)L[g] * C; t[g].v_bs = (long long)C * ldv[g]; t[g].o_bs = (long long)L[g] * C;
-        for (int b = 0; b < B[g]; ++b)
-            for (int qb = 0; qb < attn_query_blocks(L[g]); ++qb) { AttnItem& a = it[ni++]; a.problem = g; a.b = b; a.qblock = qb; a.pad_ = 0; }
+        ni += attn_group_problem(g, q[g], k[g], vT[g], out[g], B[g], L[g], C, ldv[g], t[g], it + ni);
     }
     STORM_HIP(hipMemcpyAsync(blob, host.data(), (size_t)need, hipMemcpyHostToDevice, (hipStream_t)s));
 #ifndef STORM_HOST_SIM

@@ -223,27 +223,50 @@ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // ---- grouped evaluation of P op lists of ONE network on P problems (program.hip; used by storm_ncsnpp_forward_group) -----------------------
 // The ragged micro-batches of a stream run the same op sequence on tensors of different (B, T).  Op k of every problem is launched together
-// where a grouped kernel exists for it (16-bit 3x3 convolutions of the conv_pipe family: one launch over all problems' pixel tiles),
-// one after the other otherwise.  The tables of the grouped launches (absolute device pointers) live in a caller-owned device blob.
-struct GroupOp { int k, outC, bn, kind; long long table_off, tiles_off, ntiles; const void* aux; float faux; int pad2_; const void* aux2; int x[4]; };   // kind 0: 3x3 convolution (conv_pipe), 1: GroupNorm finalize, 2: 3x3 convolution to <= 4 planes (conv_narrow; outC = input channels, bn = fused GroupNorm / SiLU flags), 3: convolution over an 8-channel input (conv_thin; outC = problems, bn = taps), 4: FIR x2 of the 8-channel pyramids (outC = channels, bn = blocks << 2 | resample), 5: fused attention (outC = channels), 6: GroupNorm-apply + SiLU + FIR x2 (outC = Ca, bn = Cb, x = {groups, resample, rows per strip << 1 | shared-activation kernel, widest problem's column blocks}, aux / aux2 = gamma / beta, faux = eps)
+// where a grouped kernel exists for it (the kinds below: one launch over all problems' tiles / items, the problem's parameters looked up in a
+// device table), one after the other otherwise.  The tables of the grouped launches (absolute device pointers) live in a caller-owned device blob.
+// In order of precedence: the first kind that matches op k owns it (program.hip's descriptor table is indexed by this enum).
+enum GroupKind {
+    GROUP_ATTENTION,      // fused attention (attention.hip)
+    GROUP_GN_FINALIZE,    // GroupNorm finalize (norm_resample.hip)
+    GROUP_GN_APPLY,       // GroupNorm-apply + SiLU + FIR x2 (norm_resample.hip)
+    GROUP_CONV_NARROW,    // 3x3 convolution to <= 4 planes (conv_narrow.hip)
+    GROUP_CONV_THIN,      // convolution over an 8-channel input (conv_thin.hip)
+    GROUP_CONV_PIPE,      // 3x3 convolution to > 128 output channels (conv_pipe.hip)
+    GROUP_KINDS
+};
+struct GnApplyGroupPlan { int rows_per_strip, share, max_cols; long long items; };
+// one grouped launch: op k of every problem as `kind`, its table of problems and its list of ntiles items / tiles at these offsets of the blob
+struct GroupOp {
+    int k;
+    GroupKind kind;
+    long long table_off, tiles_off, ntiles;
+    union {                                                  // what the kind's launch needs beside the tables
+        struct { int outC, bn; } pipe;                       // output channels, couts per workgroup (256 / 128)
+        struct { int Cin; bool has_gn, silu; } narrow;       // input channels, fused GroupNorm (scale, shift) table present, SiLU after it
+        struct { int P, ntaps; } thin;
+        struct { int groups; } finalize;
+        struct { int C; const float* bias; float scale; } attention;
+        struct { int Ca, Cb, groups, resample; GnApplyGroupPlan plan; const float* gamma; const float* beta; float eps; } apply;
+    };
+};
 // one problem of a grouped GroupNorm finalize (norm_resample.hip): the arguments of its own storm_gn_finalize(_ss) call
 struct GnFinProblem { const float* pa; const float* pb; double* stats; const float* gamma; const float* beta; float* ss; long long count;
                       int Ca, tiles_a, Cb, tiles_b; float eps; int pad_; };
 struct GnFinItem { int problem, b; };
+int launch_gn_finalize_group(const GnFinProblem* dev_tab, const void* dev_items, int n_items, int groups, hipStream_t st);
 // one problem / one workgroup of a grouped fused attention (attention.hip): the arguments of the problem's own storm_attention call
 struct AttnProblem { const void* q; const void* k; const void* vT; void* out; long long q_bs, k_bs, v_bs, o_bs; int L, ldv; };
 struct AttnItem { int problem, b, qblock, pad_; };
-int attn_query_blocks(int L);
+bool attn_group_supported(int C, int dtype);                 // 16-bit operands, a channel count the grouped kernel is built for
+long long attn_group_table_bytes(int P);                     // P AttnProblem, rounded to where the item list starts
+long long attn_group_items(int B, int L);                    // items (batch rows x query blocks) of one problem
+// fills contiguous problem g (q / k / out [B][L][C], vT [B][C][ldv]) and appends its items; returns the items written
+long long attn_group_problem(int g, const void* q, const void* k, const void* vT, void* out, int B, int L, int C, int ldv, AttnProblem& t, AttnItem* items);
 int launch_attention_group(const AttnProblem* dev_tab, const AttnItem* dev_items, int n_items, const float* bias, int C, float scale, int dtype, hipStream_t st);
-// one problem of a grouped FIR x2 launch (the 8-channel pyramids: fir_kernel): its own storm_fir_up2 / _down2 arguments + pixels per block
-struct FirProblem { const void* x; const void* add; void* out; int H, W, ppb, pad_; };
-int fir_group_problem(int resample, const void* x, const void* add, void* out, int B, int H, int W, int C, FirProblem& q);   // returns the problem's blocks
-int launch_fir_group(int resample, const FirProblem* dev_tab, const void* dev_items, int n_items, int max_blocks, int C, int dtype, hipStream_t st);
-int launch_gn_finalize_group(const GnFinProblem* dev_tab, const void* dev_items, int n_items, int groups, hipStream_t st);
 // one problem of a grouped GroupNorm-apply + SiLU + FIR x2 launch (norm_resample.hip: gn_apply_up / gn_apply_down(_share)): the arguments of its own
 // storm_gn_apply call + the geometry of the strips; items = (problem, y index of the problem's own launch) as GnFinItem
 struct GnApplyProblem { const void* xa; const void* xb; const double* stats; void* out_act; void* out_raw; int H, W, ncg, nstrips, cols, pad_; };
-struct GnApplyGroupPlan { int rows_per_strip, share, max_cols; long long items; };
 // the strips of the GROUP (any strip length / either down-sampling kernel gives the same bits: chosen by the group's workgroup count); 16-bit, SiLU only
 bool gn_apply_group_plan(int resample, int C, int P, const int* B, const int* H, const int* W, int dtype, GnApplyGroupPlan& plan);
 // fills problem g's geometry (pointers are the caller's) and appends its items; returns the items written

@@ -912,7 +912,7 @@ extern "C" int storm_conv_group(const storm_conv_args* a, int P, void* blob, lon
 #ifndef STORM_HOST_SIM
         STORM_HIP(hipStreamSynchronize((hipStream_t)s));
 #endif
-        return storm::launch_conv_narrow_group(a[0], blob, reinterpret_cast<const storm::pipe::GroupTile*>(static_cast<char*>(blob) + tabn), ntn, (hipStream_t)s);
+        return storm::launch_conv_narrow_group(a[0].dtype, a[0].seg[0].Ca, a[0].seg[0].gn_ss != nullptr, a[0].seg[0].gn_silu != 0, blob, reinterpret_cast<const storm::pipe::GroupTile*>(static_cast<char*>(blob) + tabn), ntn, (hipStream_t)s);
     }
     const long long tab = ((long long)P * (long long)sizeof(storm::pipe::PipeParams) + 255) / 256 * 256;
     storm::pipe::PipeParams* table = reinterpret_cast<storm::pipe::PipeParams*>(host.data());

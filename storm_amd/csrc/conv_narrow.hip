@@ -252,11 +252,11 @@ static int launch_narrow_group(const void* dev_table, const pipe::GroupTile* dev
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }
-int launch_conv_narrow_group(const storm_conv_args& a0, const void* dev_table, const pipe::GroupTile* dev_tiles, long long ntiles, hipStream_t st) {
+int launch_conv_narrow_group(int dtype, int Cin, bool has_gn, bool gn_silu, const void* dev_table, const pipe::GroupTile* dev_tiles, long long ntiles, hipStream_t st) {
     STORM_CHECK(dev_table && dev_tiles && ntiles > 0 && ntiles < (1LL << 31), "storm_conv (narrow group): bad arguments");
-    const bool c256 = a0.seg[0].Ca == 256, silu = a0.seg[0].gn_ss != nullptr && a0.seg[0].gn_silu != 0;
+    const bool c256 = Cin == 256, silu = has_gn && gn_silu;            // (without a fused GroupNorm operand the flag is unused)
 #define STORM_NG(T_, CG_) (silu ? launch_narrow_group<T_, CG_, true>(dev_table, dev_tiles, ntiles, st) : launch_narrow_group<T_, CG_, false>(dev_table, dev_tiles, ntiles, st))
-    if (a0.dtype == STORM_F16) return c256 ? STORM_NG(half_t, 4) : STORM_NG(half_t, 2);
+    if (dtype == STORM_F16) return c256 ? STORM_NG(half_t, 4) : STORM_NG(half_t, 2);
     return c256 ? STORM_NG(bf16_t, 4) : STORM_NG(bf16_t, 2);
 #undef STORM_NG
 }

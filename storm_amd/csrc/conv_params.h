@@ -243,7 +243,8 @@ int launch_conv_thin_group(const void* dev_image, int P, long long ntiles, int n
 long long conv_narrow_group_bytes(int P);
 long long conv_narrow_group_tiles(const storm_conv_args& a);
 long long conv_narrow_group_prepare(const storm_conv_args* a, int P, void* table, pipe::GroupTile* tiles, long long max_tiles);
-int launch_conv_narrow_group(const storm_conv_args& a0, const void* dev_table, const pipe::GroupTile* dev_tiles, long long ntiles, hipStream_t st);
+// (Cin: the layer's input channels; has_gn / gn_silu: a fused GroupNorm (scale, shift) table is applied to the input, with SiLU)
+int launch_conv_narrow_group(int dtype, int Cin, bool has_gn, bool gn_silu, const void* dev_table, const pipe::GroupTile* dev_tiles, long long ntiles, hipStream_t st);
 // defined in conv_narrow.hip: 3x3 convolutions to <= 4 output channels (the output pyramid): one 36-row 1x1 GEMM + a nine-point gather
 bool conv_narrow_supports(const storm_conv_args& a);
 int launch_conv_narrow(const storm_conv_args& a, hipStream_t st);

@@ -740,13 +740,6 @@ __global__ void fir_kernel(const T* __restrict__ x, const T* __restrict__ add, T
                            int H, int W, int C, int ppb, int C8, int PL) {
     fir_body<T, RESAMPLE>(x, add, out, H, W, C, ppb, C8, PL, blockIdx.y);
 }
-// the same for the batch items of several problems in one launch (grouped evaluation, common.h): grid.x = the largest problem's blocks
-template <typename T, int RESAMPLE>
-__global__ void fir_group_kernel(const FirProblem* __restrict__ tab, const GnFinItem* __restrict__ items, int C, int C8, int PL) {
-    const GnFinItem it = items[blockIdx.y];
-    const FirProblem& q = tab[it.problem];
-    fir_body<T, RESAMPLE>(static_cast<const T*>(q.x), static_cast<const T*>(q.add), static_cast<T*>(q.out), q.H, q.W, C, q.ppb, C8, PL, it.b);
-}
 
 template <typename T>
 static int gn_stats_t(const void* xa, int Ca, const void* xb, int Cb, int B, int HW, int G, double* stats,
@@ -887,18 +880,6 @@ static int upfirdn2d_t(const void* x, const float* k, void* out, int N, int H, i
     return STORM_OK;
 }
 
-// grouped FIR x2 (8-channel pyramids): fills one problem's table entry and returns its block count
-template <int R>
-static int fir_problem(const void* x, const void* add, void* out, int B, int H, int W, int C, FirProblem& q) {
-    const GnGeom g = gn_geom(C);
-    const int OHW = R == 1 ? 4 * H * W : H * W / 4;
-    q.x = x; q.add = add; q.out = out; q.H = H; q.W = W;
-    q.ppb = g.PL * pixels_per_thread((long long)B * OHW, g.PL, 32);
-    return cdiv(OHW, q.ppb);
-}
-int fir_group_problem(int resample, const void* x, const void* add, void* out, int B, int H, int W, int C, FirProblem& q) {
-    return resample == 1 ? fir_problem<1>(x, add, out, B, H, W, C, q) : fir_problem<2>(x, add, out, B, H, W, C, q);
-}
 // ---- grouped GroupNorm-apply + SiLU + FIR x2 (common.h) -----------------------------------------------------------------------------------
 bool gn_apply_group_plan(int resample, int C, int P, const int* B, const int* H, const int* W, int dtype, GnApplyGroupPlan& plan) {
     if ((dtype != STORM_BF16 && dtype != STORM_F16) || (resample != 1 && resample != 2) || C % 8 != 0 || C > GN_MAX_C) return false;
@@ -941,19 +922,6 @@ int launch_gn_apply_group(int resample, const GnApplyProblem* dev_tab, const voi
     if (dtype == STORM_BF16) gn_apply_group_t<bf16_t>(resample, dev_tab, it, plan, Ca, Cb, G, gamma, beta, eps, st);
     else if (dtype == STORM_F16) gn_apply_group_t<half_t>(resample, dev_tab, it, plan, Ca, Cb, G, gamma, beta, eps, st);
     else STORM_CHECK(false, "storm_gn_apply (group): dtype %d", dtype);
-    STORM_LAUNCH_CHECK();
-    return STORM_OK;
-}
-
-int launch_fir_group(int resample, const FirProblem* dev_tab, const void* dev_items, int n_items, int max_blocks, int C, int dtype, hipStream_t st) {
-    STORM_CHECK(dev_tab && dev_items && n_items > 0 && n_items < 65536 && max_blocks > 0 && C % 8 == 0 && C <= GN_MAX_C, "storm_fir (group): bad arguments");
-    const GnGeom g = gn_geom(C);
-    const GnFinItem* it = static_cast<const GnFinItem*>(dev_items);
-#define STORM_FIRG(T_, R_) hipLaunchKernelGGL((fir_group_kernel<T_, R_>), dim3(max_blocks, n_items), dim3(g.NT), 0, st, dev_tab, it, C, g.C8, g.PL)
-    if (dtype == STORM_BF16) { if (resample == 1) STORM_FIRG(bf16_t, 1); else STORM_FIRG(bf16_t, 2); }
-    else if (dtype == STORM_F16) { if (resample == 1) STORM_FIRG(half_t, 1); else STORM_FIRG(half_t, 2); }
-    else { if (resample == 1) STORM_FIRG(float, 1); else STORM_FIRG(float, 2); }
-#undef STORM_FIRG
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }

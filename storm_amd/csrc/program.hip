@@ -8,10 +8,19 @@
 
 using namespace storm;
 
-static inline void* resolve(const storm_ref& r, void* const* bufs, int n_bufs, bool& ok) {
-    if (r.buf < 0) return nullptr;
-    if (r.buf >= n_bufs || bufs[r.buf] == nullptr) { ok = false; return nullptr; }
-    return static_cast<char*>(bufs[r.buf]) + r.off;
+// the STORM_OP_NPTR references of an op against one problem's buffers (g: the problem of a grouped evaluation, < 0 = storm_program_run's own list)
+static int resolve_op(const storm_op& op, void* const* bufs, int n_bufs, int k, int g, void** p) {
+    bool ok = true;
+    for (int j = 0; j < STORM_OP_NPTR; ++j) {
+        const storm_ref& r = op.p[j];
+        p[j] = nullptr;
+        if (r.buf < 0) continue;
+        if (r.buf >= n_bufs || bufs[r.buf] == nullptr) ok = false;
+        else p[j] = static_cast<char*>(bufs[r.buf]) + r.off;
+    }
+    if (g < 0) STORM_CHECK(ok, "storm_program_run: op %d (code %d) references a missing buffer", k, op.code);
+    else STORM_CHECK(ok, "storm_program_group: op %d of problem %d references a missing buffer", k, g);
+    return STORM_OK;
 }
 
 // storm_conv_args of a STORM_OP_CONV op (pointers resolved by the caller; NULL pointers when only the shape matters)
@@ -51,10 +60,8 @@ static int run_ops(const storm_op* ops, int n_ops, void* const* bufs, int n_bufs
     for (int k = 0; k < n_ops; ++k) {
         if (ev) STORM_HIP(hipEventRecord(ev[k], st));
         const storm_op& op = ops[k];
-        bool ok = true;
         void* p[STORM_OP_NPTR];
-        for (int j = 0; j < STORM_OP_NPTR; ++j) p[j] = resolve(op.p[j], bufs, n_bufs, ok);
-        STORM_CHECK(ok, "storm_program_run: op %d (code %d) references a missing buffer", k, op.code);
+        if (int rc = resolve_op(op, bufs, n_bufs, k, -1, p)) return rc;
         const int64_t* i = op.i;
         int rc = STORM_OK;
         switch (op.code) {
@@ -138,84 +145,93 @@ static int run_ops(const storm_op* ops, int n_ops, void* const* bufs, int n_bufs
 
 
 // ---- grouped evaluation (common.h) ---------------------------------------------------------------------------------------------------------
+// One descriptor per grouped kind (GROUP_TABLE): match says whether op k of the P lists is this kind and computes its geometry ONCE - the sizing
+// (program_group_blob_bytes) and the fill (program_group_build) consume the same GroupGeom; fill writes the host image of the kind's table and item
+// list and the launch record of its GroupOp; launch runs it from the device copy (program_run_group).  No other function enumerates kinds.
 namespace {
-// op k of the P lists groups when it is the same 16-bit 3x3 convolution of the conv_pipe family in every problem
-bool group_candidate(const storm_op* const* ops, int k, int P, int dtype) {
-    if (dtype != STORM_BF16 && dtype != STORM_F16) return false;
-    if (switches().conv_variant >= 0) return false;          // a forced kernel family (tests, A/B) is honoured problem by problem
-    for (int g = 0; g < P; ++g) {
-        const storm_op& o = ops[g][k];
-        if (o.code != STORM_OP_CONV) return false;
-        if ((int)o.i[4] <= 128 || (int)o.i[7] != 0 || (int)o.i[8 + 4] != 9) return false;      // outC, out_f32, taps of segment 0
-        if (o.i[4] != ops[0][k].i[4] || o.i[5] != ops[0][k].i[5] || o.i[0] != ops[0][k].i[0]) return false;
-    }
-    return true;
-}
-long long op_tiles(const storm_op& o) { return (long long)o.i[1] * cdiv(o.i[2], 8) * cdiv(o.i[3], 32); }   // B x 8-row x 32-pixel tiles
-// the output pyramid's 3x3 convolutions to <= 4 planes (conv_narrow.hip): 4 per evaluation, one 8-wave workgroup per CU walking 20 x 32-pixel tiles
-bool narrow_candidate(const storm_op* const* ops, int k, int P, int dtype) {
-    if (dtype != STORM_BF16 && dtype != STORM_F16) return false;
-    if (switches().conv_variant >= 0) return false;
-    for (int g = 0; g < P; ++g) {
-        const storm_op& o = ops[g][k];
-        if (o.code != STORM_OP_CONV || (int)o.i[4] != 8 || (int)o.i[0] != 1 || (int)o.i[8 + 4] != 9 || (int)o.i[7] != 0) return false;
-        if (o.i[5] != ops[0][k].i[5] || o.i[8] != ops[0][k].i[8] || o.i[9] != 0) return false;
-    }
-    return true;
-}
-// the 8-channel-input convolutions (conv_thin.hip: the stem and the three input-skip 1x1s)
-bool thin_candidate(const storm_op* const* ops, int k, int P, int dtype) {
-    if (dtype != STORM_BF16 && dtype != STORM_F16) return false;
-    if (switches().conv_variant >= 0) return false;
-    for (int g = 0; g < P; ++g) {
-        const storm_op& o = ops[g][k];
-        if (o.code != STORM_OP_CONV || (int)o.i[0] != 1 || (int)o.i[8] != 8 || (int)o.i[9] != 0 || (int)o.i[4] < 64 || (int)o.i[7] != 0) return false;
-        if (o.i[4] != ops[0][k].i[4] || o.i[8 + 4] != ops[0][k].i[8 + 4]) return false;
-    }
-    return true;
-}
-long long narrow_tiles(const storm_op& o) { return (long long)o.i[1] * cdiv(o.i[2], 20) * cdiv(o.i[3], 32); }
+struct GroupGeom { long long table_bytes, tiles_bytes, items; GnApplyGroupPlan apply; };   // bytes of the problems' table and of the item / tile list, its entries
+// the P lists and the problems' buffers of one program_group_build call (args: scratch of the convolution kinds)
+struct GroupCtx { const storm_op* const* ops; void* const* const* bufs; int n_bufs, P, dtype; std::vector<storm_conv_args> args; };
+struct GroupDesc {
+    bool (*match)(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo);
+    // 1 = filled, 0 = not groupable after all (the op runs problem by problem), < 0 = error
+    int (*fill)(GroupCtx& c, int k, const GroupGeom& geo, char* table, char* tiles, GroupOp& go);
+    int (*launch)(const GroupOp& go, const char* dev_table, const char* dev_tiles, int dtype, hipStream_t st);
+};
+
 long long align256(long long v) { return (v + 255) / 256 * 256; }
-}  // namespace
+bool is16(int dtype) { return dtype == STORM_BF16 || dtype == STORM_F16; }
 
-// the GroupNorm finalizes (45 per evaluation, ~6 us each whatever the problem's size): same group count in every problem
-static bool fin_candidate(const storm_op* const* ops, int k, int P) {
-    for (int g = 0; g < P; ++g) {
-        const storm_op& o = ops[g][k];
-        if (o.code != STORM_OP_GN_FINALIZE || o.i[5] != ops[0][k].i[5] || o.i[0] + o.i[2] != ops[0][k].i[0] + ops[0][k].i[2]) return false;
-    }
-    return true;
-}
-
-// the fused attention of the bottleneck (16-bit): STORM_OP_ATTENTION (q, k, vT, bias, out, scratch; B, L, C, ldv; scale)
-static bool attn_candidate(const storm_op* const* ops, int k, int P, int dtype) {
-    if (dtype != STORM_BF16 && dtype != STORM_F16) return false;
-    for (int g = 0; g < P; ++g) {
-        const storm_op& o = ops[g][k];
-        if (o.code != STORM_OP_ATTENTION || o.i[2] != ops[0][k].i[2] || o.f[0] != ops[0][k].f[0]) return false;
-    }
-    return true;
-}
-static long long attn_items(const storm_op* const* ops, int k, int P) {
-    long long n = 0;
-    for (int g = 0; g < P; ++g) n += ops[g][k].i[0] * attn_query_blocks((int)ops[g][k].i[1]);
-    return n;
-}
-
-static bool fir_candidate(const storm_op* const* ops, int k, int P) {
-    for (int g = 0; g < P; ++g) {
-        const storm_op& o = ops[g][k];
-        if ((o.code != STORM_OP_FIR_UP && o.code != STORM_OP_FIR_DOWN) || o.code != ops[0][k].code || o.i[3] != ops[0][k].i[3]) return false;
-    }
-    return true;
-}
-
-// GroupNorm-apply + SiLU + FIR x2 of h and x (the up / down resblocks' first op: STORM_OP_GN_APPLY with resample 1 / 2): same channels, groups and
-// affine parameters in every problem
-static bool apply_candidate(const storm_op* const* ops, int k, int P, int dtype, GnApplyGroupPlan* plan) {
-    if (dtype != STORM_BF16 && dtype != STORM_F16) return false;
+// -- fused attention of the bottleneck: STORM_OP_ATTENTION (q, k, vT, bias, out, scratch; B, L, C, ldv; scale), same channels and scale in every problem
+bool attn_match(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo) {
     const storm_op& o0 = ops[0][k];
-    if (o0.code != STORM_OP_GN_APPLY || (o0.i[7] != 1 && o0.i[7] != 2) || o0.i[6] == 0 || P > 64) return false;
+    if (o0.code != STORM_OP_ATTENTION || !attn_group_supported((int)o0.i[2], dtype)) return false;
+    geo.items = 0;
+    for (int g = 0; g < P; ++g) {
+        const storm_op& o = ops[g][k];
+        if (o.code != STORM_OP_ATTENTION || o.i[2] != o0.i[2] || o.f[0] != o0.f[0]) return false;
+        geo.items += attn_group_items((int)o.i[0], (int)o.i[1]);
+    }
+    geo.table_bytes = attn_group_table_bytes(P); geo.tiles_bytes = align256(geo.items * (long long)sizeof(AttnItem));
+    return geo.items < (1LL << 31);                          // (the launch's grid.x)
+}
+int attn_fill(GroupCtx& c, int k, const GroupGeom&, char* table, char* tiles, GroupOp& go) {
+    AttnProblem* t = reinterpret_cast<AttnProblem*>(table);
+    AttnItem* it = reinterpret_cast<AttnItem*>(tiles);
+    long long ni = 0;
+    void* p[STORM_OP_NPTR];
+    for (int g = 0; g < c.P; ++g) {
+        const storm_op& o = c.ops[g][k];
+        if (int rc = resolve_op(o, c.bufs[g], c.n_bufs, k, g, p)) return rc;
+        ni += attn_group_problem(g, p[0], p[1], p[2], p[4], (int)o.i[0], (int)o.i[1], (int)o.i[2], (int)o.i[3], t[g], it + ni);
+    }
+    go.attention.C = (int)c.ops[0][k].i[2]; go.attention.bias = static_cast<const float*>(p[3]); go.attention.scale = c.ops[0][k].f[0];
+    return 1;
+}
+int attn_launch(const GroupOp& go, const char* dev_table, const char* dev_tiles, int dtype, hipStream_t st) {
+    return launch_attention_group(reinterpret_cast<const AttnProblem*>(dev_table), reinterpret_cast<const AttnItem*>(dev_tiles), (int)go.ntiles, go.attention.bias,
+                                  go.attention.C, go.attention.scale, dtype, st);
+}
+
+// -- the GroupNorm finalizes (45 per evaluation, ~6 us each whatever the problem's size): same channels and group count in every problem
+bool fin_match(const storm_op* const* ops, int k, int P, int, GroupGeom& geo) {
+    const storm_op& o0 = ops[0][k];
+    geo.items = 0;
+    for (int g = 0; g < P; ++g) {
+        const storm_op& o = ops[g][k];
+        if (o.code != STORM_OP_GN_FINALIZE || o.i[5] != o0.i[5] || o.i[0] + o.i[2] != o0.i[0] + o0.i[2]) return false;
+        geo.items += o.i[4];
+    }
+    geo.table_bytes = align256((long long)P * sizeof(GnFinProblem)); geo.tiles_bytes = align256(geo.items * (long long)sizeof(GnFinItem));
+    return geo.items < 65536;                                // (the launch's grid.y)
+}
+int fin_fill(GroupCtx& c, int k, const GroupGeom&, char* table, char* tiles, GroupOp& go) {
+    GnFinProblem* t = reinterpret_cast<GnFinProblem*>(table);
+    GnFinItem* it = reinterpret_cast<GnFinItem*>(tiles);
+    for (int g = 0; g < c.P; ++g) {
+        const storm_op& o = c.ops[g][k];
+        void* p[STORM_OP_NPTR];
+        if (int rc = resolve_op(o, c.bufs[g], c.n_bufs, k, g, p)) return rc;
+        // run_ops: GN_FINALIZE (pa, pb, stats, gamma, beta, ss; Ca, tiles_a, Cb, tiles_b, B, G, count; eps)
+        GnFinProblem& q = t[g];
+        memset(&q, 0, sizeof(q));
+        q.pa = (const float*)p[0]; q.pb = (const float*)p[1]; q.stats = (double*)p[2]; q.gamma = (const float*)p[3]; q.beta = (const float*)p[4];
+        q.ss = (float*)p[5]; q.count = p[5] != nullptr ? (long long)o.i[6] : 0; q.Ca = (int)o.i[0]; q.tiles_a = (int)o.i[1]; q.Cb = (int)o.i[2];
+        q.tiles_b = (int)o.i[3]; q.eps = p[5] != nullptr ? o.f[0] : 0.f;
+        for (int b = 0; b < (int)o.i[4]; ++b) { it->problem = g; it->b = b; ++it; }
+    }
+    go.finalize.groups = (int)c.ops[0][k].i[5];
+    return 1;
+}
+int fin_launch(const GroupOp& go, const char* dev_table, const char* dev_tiles, int, hipStream_t st) {
+    return launch_gn_finalize_group(reinterpret_cast<const GnFinProblem*>(dev_table), dev_tiles, (int)go.ntiles, go.finalize.groups, st);
+}
+
+// -- GroupNorm-apply + SiLU + FIR x2 of h and x (the up / down resblocks' first op: STORM_OP_GN_APPLY with resample 1 / 2): same channels, groups and
+// affine parameters in every problem
+bool apply_match(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo) {
+    const storm_op& o0 = ops[0][k];
+    if (!is16(dtype) || o0.code != STORM_OP_GN_APPLY || (o0.i[7] != 1 && o0.i[7] != 2) || o0.i[6] == 0 || P > 64) return false;
     int B[64], H[64], W[64];
     for (int g = 0; g < P; ++g) {
         const storm_op& o = ops[g][k];
@@ -223,41 +239,149 @@ static bool apply_candidate(const storm_op* const* ops, int k, int P, int dtype,
         if (o.p[6].buf < 0) return false;                    // (the resampling form always writes both tensors)
         B[g] = (int)o.i[2]; H[g] = (int)o.i[3]; W[g] = (int)o.i[4];
     }
-    GnApplyGroupPlan pl;
-    if (!gn_apply_group_plan((int)o0.i[7], (int)(o0.i[0] + o0.i[1]), P, B, H, W, dtype, pl)) return false;
-    if (plan) *plan = pl;
+    if (!gn_apply_group_plan((int)o0.i[7], (int)(o0.i[0] + o0.i[1]), P, B, H, W, dtype, geo.apply)) return false;
+    geo.items = geo.apply.items;
+    geo.table_bytes = align256((long long)P * sizeof(GnApplyProblem)); geo.tiles_bytes = align256(geo.items * (long long)sizeof(GnFinItem));
     return true;
 }
+int apply_fill(GroupCtx& c, int k, const GroupGeom& geo, char* table, char* tiles, GroupOp& go) {
+    GnApplyProblem* t = reinterpret_cast<GnApplyProblem*>(table);
+    GnFinItem* it = reinterpret_cast<GnFinItem*>(tiles);
+    const storm_op& o0 = c.ops[0][k];
+    long long ni = 0;
+    void* p[STORM_OP_NPTR];
+    for (int g = 0; g < c.P; ++g) {
+        const storm_op& o = c.ops[g][k];
+        if (int rc = resolve_op(o, c.bufs[g], c.n_bufs, k, g, p)) return rc;
+        // run_ops: GN_APPLY (xa, xb, stats, gamma, beta, out_act, out_raw; Ca, Cb, B, H, W, G, silu, resample; eps)
+        GnApplyProblem& q = t[g];
+        memset(&q, 0, sizeof(q));
+        q.xa = p[0]; q.xb = p[1]; q.stats = (const double*)p[2]; q.out_act = p[5]; q.out_raw = p[6]; q.H = (int)o.i[3]; q.W = (int)o.i[4];
+        ni += gn_apply_group_problem((int)o0.i[7], (int)(o0.i[0] + o0.i[1]), (int)o.i[2], c.dtype, geo.apply, g, q, it + ni);
+    }
+    STORM_CHECK(ni == geo.items, "storm_program_group: GroupNorm-apply items %lld != %lld", ni, geo.items);
+    go.apply.Ca = (int)o0.i[0]; go.apply.Cb = (int)o0.i[1]; go.apply.groups = (int)o0.i[5]; go.apply.resample = (int)o0.i[7]; go.apply.plan = geo.apply;
+    go.apply.gamma = static_cast<const float*>(p[3]); go.apply.beta = static_cast<const float*>(p[4]); go.apply.eps = o0.f[0];
+    return 1;
+}
+int apply_launch(const GroupOp& go, const char* dev_table, const char* dev_tiles, int dtype, hipStream_t st) {
+    return launch_gn_apply_group(go.apply.resample, reinterpret_cast<const GnApplyProblem*>(dev_table), dev_tiles, go.apply.plan, go.apply.Ca, go.apply.Cb, go.apply.groups,
+                                 go.apply.gamma, go.apply.beta, go.apply.eps, dtype, st);
+}
+
+// -- the three 16-bit convolution kinds.  STORM_OP_CONV: i[0] segments, i[1..3] B H W, i[4] outC, i[5] Cout, i[7] out_f32, i[8..] segment 0's Ca, Cb, CinP, rows, taps
+bool conv_match(const storm_op& o, int dtype) {
+    return is16(dtype) && switches().conv_variant < 0 &&     // a forced kernel family (tests, A/B) is honoured problem by problem
+           o.code == STORM_OP_CONV && (int)o.i[7] == 0;
+}
+long long conv_tiles(const storm_op* const* ops, int k, int P, int th, int tw) {   // B x th-row x tw-pixel tiles of all problems
+    long long t = 0;
+    for (int g = 0; g < P; ++g) t += (long long)ops[g][k].i[1] * cdiv(ops[g][k].i[2], th) * cdiv(ops[g][k].i[3], tw);
+    return t;
+}
+// storm_conv_args of op k of every problem in c.args
+int conv_group_args(GroupCtx& c, int k) {
+    c.args.resize((size_t)c.P);
+    for (int g = 0; g < c.P; ++g) {
+        void* p[STORM_OP_NPTR];
+        if (int rc = resolve_op(c.ops[g][k], c.bufs[g], c.n_bufs, k, g, p)) return rc;
+        conv_args_of(c.ops[g][k], p, c.dtype, c.args[(size_t)g]);
+        c.args[(size_t)g].splitk_ws = nullptr; c.args[(size_t)g].splitk_ws_bytes = 0;      // (a grouped launch never splits K)
+    }
+    return STORM_OK;
+}
+
+// the output pyramid's 3x3 convolutions to <= 4 planes (conv_narrow.hip): 4 per evaluation, one 8-wave workgroup per CU walking 20 x 32-pixel tiles
+bool narrow_match(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo) {
+    for (int g = 0; g < P; ++g) {
+        const storm_op& o = ops[g][k];
+        if (!conv_match(o, dtype) || (int)o.i[4] != 8 || (int)o.i[0] != 1 || (int)o.i[8 + 4] != 9) return false;
+        if (o.i[5] != ops[0][k].i[5] || o.i[8] != ops[0][k].i[8] || o.i[9] != 0) return false;
+    }
+    geo.items = conv_tiles(ops, k, P, 20, 32);
+    geo.table_bytes = conv_narrow_group_bytes(P); geo.tiles_bytes = align256(geo.items * (long long)sizeof(pipe::GroupTile));
+    return true;
+}
+int narrow_fill(GroupCtx& c, int k, const GroupGeom& geo, char* table, char* tiles, GroupOp& go) {
+    if (int rc = conv_group_args(c, k)) return rc;
+    if (conv_narrow_group_prepare(c.args.data(), c.P, table, reinterpret_cast<pipe::GroupTile*>(tiles), geo.items) != geo.items) return 0;
+    const storm_conv_seg& s0 = c.args[0].seg[0];
+    go.narrow.Cin = s0.Ca; go.narrow.has_gn = s0.gn_ss != nullptr; go.narrow.silu = s0.gn_silu != 0;
+    return 1;
+}
+int narrow_launch(const GroupOp& go, const char* dev_table, const char* dev_tiles, int dtype, hipStream_t st) {
+    return launch_conv_narrow_group(dtype, go.narrow.Cin, go.narrow.has_gn, go.narrow.silu, dev_table, reinterpret_cast<const pipe::GroupTile*>(dev_tiles), go.ntiles, st);
+}
+
+// the 8-channel-input convolutions (conv_thin.hip: the stem and the three input-skip 1x1s); the image is one piece (its tile count is fill's)
+bool thin_match(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo) {
+    for (int g = 0; g < P; ++g) {
+        const storm_op& o = ops[g][k];
+        if (!conv_match(o, dtype) || (int)o.i[0] != 1 || (int)o.i[8] != 8 || (int)o.i[9] != 0 || (int)o.i[4] < 64) return false;
+        if (o.i[4] != ops[0][k].i[4] || o.i[8 + 4] != ops[0][k].i[8 + 4]) return false;
+    }
+    geo.items = 0; geo.table_bytes = conv_thin_group_bytes(P); geo.tiles_bytes = 0;
+    return true;
+}
+int thin_fill(GroupCtx& c, int k, const GroupGeom&, char* table, char*, GroupOp& go) {
+    if (int rc = conv_group_args(c, k)) return rc;
+    go.ntiles = conv_thin_group_prepare(c.args.data(), c.P, table);
+    if (go.ntiles <= 0) return 0;
+    go.thin.P = c.P; go.thin.ntaps = c.args[0].seg[0].ntaps;
+    return 1;
+}
+int thin_launch(const GroupOp& go, const char* dev_table, const char*, int dtype, hipStream_t st) {
+    return launch_conv_thin_group(dev_table, go.thin.P, go.ntiles, go.thin.ntaps, dtype, st);
+}
+
+// the same 3x3 convolution of the conv_pipe family (> 128 output channels) in every problem: 8-row x 32-pixel tiles
+bool pipe_match(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo) {
+    for (int g = 0; g < P; ++g) {
+        const storm_op& o = ops[g][k];
+        if (!conv_match(o, dtype) || (int)o.i[4] <= 128 || (int)o.i[8 + 4] != 9) return false;
+        if (o.i[4] != ops[0][k].i[4] || o.i[5] != ops[0][k].i[5] || o.i[0] != ops[0][k].i[0]) return false;
+    }
+    geo.items = conv_tiles(ops, k, P, 8, 32);
+    geo.table_bytes = align256((long long)P * sizeof(pipe::PipeParams)); geo.tiles_bytes = align256(geo.items * (long long)sizeof(pipe::GroupTile));
+    return true;
+}
+int pipe_fill(GroupCtx& c, int k, const GroupGeom& geo, char* table, char* tiles, GroupOp& go) {
+    if (int rc = conv_group_args(c, k)) return rc;
+    if (conv_pipe_group_prepare(c.args.data(), c.P, reinterpret_cast<pipe::PipeParams*>(table), reinterpret_cast<pipe::GroupTile*>(tiles), geo.items) != geo.items)
+        return 0;                                            // outside the pipelined kernel's coverage
+    go.pipe.outC = c.args[0].outC;
+    go.pipe.bn = geo.items * cdiv(go.pipe.outC, 256) >= 512 ? 256 : 128;   // the ladder's rule for the pipelined kernel's two tiles, on the GROUP's tile count
+    return 1;
+}
+int pipe_launch(const GroupOp& go, const char* dev_table, const char* dev_tiles, int dtype, hipStream_t st) {
+    return launch_conv_pipe_group(reinterpret_cast<const pipe::PipeParams*>(dev_table), reinterpret_cast<const pipe::GroupTile*>(dev_tiles), go.ntiles, go.pipe.outC,
+                                  go.pipe.bn, dtype, st);
+}
+
+// indexed by GroupKind, which is the order of precedence: the FIRST kind that matches op k owns it (narrow before thin before pipe) - where its
+// fill then declines, the op runs problem by problem, it is not offered to the next kind
+const GroupDesc GROUP_TABLE[GROUP_KINDS] = {
+    {attn_match, attn_fill, attn_launch},         // GROUP_ATTENTION
+    {fin_match, fin_fill, fin_launch},            // GROUP_GN_FINALIZE
+    {apply_match, apply_fill, apply_launch},      // GROUP_GN_APPLY
+    {narrow_match, narrow_fill, narrow_launch},   // GROUP_CONV_NARROW
+    {thin_match, thin_fill, thin_launch},         // GROUP_CONV_THIN
+    {pipe_match, pipe_fill, pipe_launch},         // GROUP_CONV_PIPE
+};
+// the kind of op k of the P lists and its geometry; GROUP_KINDS = none
+int group_kind_of(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo) {
+    int kind = 0;
+    while (kind < GROUP_KINDS && !GROUP_TABLE[kind].match(ops, k, P, dtype, geo)) ++kind;
+    return kind;
+}
+}  // namespace
 
 long long storm::program_group_blob_bytes(const storm_op* const* ops, int n_ops, int P, int dtype) {
     long long n = 0;
     if (P < 2) return 0;
     for (int k = 0; k < n_ops; ++k) {
-        if (fir_candidate(ops, k, P)) {
-            long long items = 0;
-            for (int g = 0; g < P; ++g) items += ops[g][k].i[0];
-            n += align256((long long)P * sizeof(FirProblem)) + align256(items * 8);
-            continue;
-        }
-        if (attn_candidate(ops, k, P, dtype)) { n += align256((long long)P * sizeof(AttnProblem)) + align256(attn_items(ops, k, P) * (long long)sizeof(AttnItem)); continue; }
-        if (fin_candidate(ops, k, P)) {
-            long long items = 0;
-            for (int g = 0; g < P; ++g) items += ops[g][k].i[4];
-            n += align256((long long)P * sizeof(GnFinProblem)) + align256(items * 8);
-            continue;
-        }
-        { GnApplyGroupPlan pl; if (apply_candidate(ops, k, P, dtype, &pl)) { n += align256((long long)P * sizeof(GnApplyProblem)) + align256(pl.items * 8); continue; } }
-        if (narrow_candidate(ops, k, P, dtype)) {
-            long long t = 0;
-            for (int g = 0; g < P; ++g) t += narrow_tiles(ops[g][k]);
-            n += conv_narrow_group_bytes(P) + align256(t * (long long)sizeof(pipe::GroupTile));
-            continue;
-        }
-        if (thin_candidate(ops, k, P, dtype)) { n += conv_thin_group_bytes(P); continue; }
-        if (!group_candidate(ops, k, P, dtype)) continue;
-        long long t = 0;
-        for (int g = 0; g < P; ++g) t += op_tiles(ops[g][k]);
-        n += align256((long long)P * sizeof(pipe::PipeParams)) + align256(t * (long long)sizeof(pipe::GroupTile));
+        GroupGeom geo;
+        if (group_kind_of(ops, k, P, dtype, geo) < GROUP_KINDS) n += geo.table_bytes + geo.tiles_bytes;
     }
     return n;
 }
@@ -266,170 +390,25 @@ int storm::program_group_build(const storm_op* const* ops, int n_ops, void* cons
                                long long blob_bytes, GroupOp* gops, int max_gops, int stable_bufs) {
     int n = 0;
     long long off = 0;
-    std::vector<storm_conv_args> args((size_t)P);
+    GroupCtx c{ops, bufs, n_bufs, P, dtype, {}};
     for (int k = 0; k < n_ops; ++k) {
         bool stable = true;                                  // (tables are rebuilt only when a stable buffer moves: nothing else may be in them)
         for (int g = 0; g < P && stable; ++g)
             for (int j = 0; j < STORM_OP_NPTR; ++j) stable = stable && ops[g][k].p[j].buf < stable_bufs;
         if (!stable) continue;
-        if (fir_candidate(ops, k, P)) {
-            long long items = 0;
-            for (int g = 0; g < P; ++g) items += ops[g][k].i[0];
-            const long long tab = align256((long long)P * sizeof(FirProblem)), til = align256(items * 8);
-            STORM_CHECK(off + tab + til <= blob_bytes && n < max_gops && items < 65536, "storm_program_group: table blob too small");
-            FirProblem* t = reinterpret_cast<FirProblem*>(host_blob + off);
-            int* it = reinterpret_cast<int*>(host_blob + off + tab);
-            const int up = ops[0][k].code == STORM_OP_FIR_UP ? 1 : 2;
-            long long ni = 0;
-            int max_blocks = 0;
-            for (int g = 0; g < P; ++g) {
-                const storm_op& o = ops[g][k];
-                bool ok = true;
-                void* p[STORM_OP_NPTR];
-                for (int j = 0; j < STORM_OP_NPTR; ++j) p[j] = resolve(o.p[j], bufs[g], n_bufs, ok);
-                STORM_CHECK(ok, "storm_program_group: op %d of problem %d references a missing buffer", k, g);
-                memset(&t[g], 0, sizeof(FirProblem));
-                // run_ops: FIR_UP (x, add, out; B, H, W, C) / FIR_DOWN (x, out; B, H, W, C)
-                const int nb = up == 1 ? fir_group_problem(1, p[0], p[1], p[2], (int)o.i[0], (int)o.i[1], (int)o.i[2], (int)o.i[3], t[g])
-                                       : fir_group_problem(2, p[0], nullptr, p[1], (int)o.i[0], (int)o.i[1], (int)o.i[2], (int)o.i[3], t[g]);
-                if (nb > max_blocks) max_blocks = nb;
-                for (int b = 0; b < (int)o.i[0]; ++b) { it[2 * ni] = g; it[2 * ni + 1] = b; ++ni; }
-            }
-            GroupOp& go = gops[n++];
-            go.k = k; go.kind = 4; go.outC = (int)ops[0][k].i[3]; go.bn = (max_blocks << 2) | up; go.table_off = off; go.tiles_off = off + tab; go.ntiles = ni;
-            off += tab + til;
-            continue;
-        }
-        if (attn_candidate(ops, k, P, dtype)) {
-            const long long items = attn_items(ops, k, P);
-            const long long tab = align256((long long)P * sizeof(AttnProblem)), til = align256(items * (long long)sizeof(AttnItem));
-            STORM_CHECK(off + tab + til <= blob_bytes && n < max_gops && items < (1LL << 31), "storm_program_group: table blob too small");
-            AttnProblem* t = reinterpret_cast<AttnProblem*>(host_blob + off);
-            AttnItem* it = reinterpret_cast<AttnItem*>(host_blob + off + tab);
-            long long ni = 0;
-            const void* bias = nullptr;
-            for (int g = 0; g < P; ++g) {
-                const storm_op& o = ops[g][k];
-                bool ok = true;
-                void* p[STORM_OP_NPTR];
-                for (int j = 0; j < STORM_OP_NPTR; ++j) p[j] = resolve(o.p[j], bufs[g], n_bufs, ok);
-                STORM_CHECK(ok, "storm_program_group: op %d of problem %d references a missing buffer", k, g);
-                const int B = (int)o.i[0], L = (int)o.i[1], Cc = (int)o.i[2], ldv = (int)o.i[3];
-                AttnProblem& q = t[g];
-                memset(&q, 0, sizeof(q));
-                q.q = p[0]; q.k = p[1]; q.vT = p[2]; q.out = p[4]; q.L = L; q.ldv = ldv;
-                q.q_bs = (long long)L * Cc; q.k_bs = (long long)L * Cc; q.v_bs = (long long)Cc * ldv; q.o_bs = (long long)L * Cc;     // (run_ops' strides)
-                bias = p[3];
-                const int nq = attn_query_blocks(L);
-                // long rows first inside the list would balance better; the order is the problems' (deterministic, the result does not depend on it)
-                for (int b = 0; b < B; ++b)
-                    for (int qb = 0; qb < nq; ++qb) { AttnItem& a = it[ni++]; a.problem = g; a.b = b; a.qblock = qb; a.pad_ = 0; }
-            }
-            GroupOp& go = gops[n++];
-            go.k = k; go.kind = 5; go.outC = (int)ops[0][k].i[2]; go.bn = 0; go.table_off = off; go.tiles_off = off + tab; go.ntiles = ni;
-            go.aux = bias; go.faux = ops[0][k].f[0];
-            off += tab + til;
-            continue;
-        }
-        if (fin_candidate(ops, k, P)) {
-            long long items = 0;
-            for (int g = 0; g < P; ++g) items += ops[g][k].i[4];
-            const long long tab = align256((long long)P * sizeof(GnFinProblem)), til = align256(items * 8);
-            STORM_CHECK(off + tab + til <= blob_bytes && n < max_gops && items < 65536, "storm_program_group: table blob too small");
-            GnFinProblem* t = reinterpret_cast<GnFinProblem*>(host_blob + off);
-            int* it = reinterpret_cast<int*>(host_blob + off + tab);
-            long long ni = 0;
-            for (int g = 0; g < P; ++g) {
-                const storm_op& o = ops[g][k];
-                bool ok = true;
-                void* p[STORM_OP_NPTR];
-                for (int j = 0; j < STORM_OP_NPTR; ++j) p[j] = resolve(o.p[j], bufs[g], n_bufs, ok);
-                STORM_CHECK(ok, "storm_program_group: op %d of problem %d references a missing buffer", k, g);
-                GnFinProblem& q = t[g];
-                memset(&q, 0, sizeof(q));
-                q.pa = (const float*)p[0]; q.pb = (const float*)p[1]; q.stats = (double*)p[2]; q.gamma = (const float*)p[3]; q.beta = (const float*)p[4];
-                q.ss = (float*)p[5]; q.count = p[5] != nullptr ? (long long)o.i[6] : 0; q.Ca = (int)o.i[0]; q.tiles_a = (int)o.i[1]; q.Cb = (int)o.i[2];
-                q.tiles_b = (int)o.i[3]; q.eps = p[5] != nullptr ? o.f[0] : 0.f;
-                for (int b = 0; b < (int)o.i[4]; ++b) { it[2 * ni] = g; it[2 * ni + 1] = b; ++ni; }
-            }
-            GroupOp& go = gops[n++];
-            go.k = k; go.kind = 1; go.outC = (int)ops[0][k].i[5]; go.bn = 0; go.table_off = off; go.tiles_off = off + tab; go.ntiles = ni;
-            off += tab + til;
-            continue;
-        }
-        { GnApplyGroupPlan pl;
-          if (apply_candidate(ops, k, P, dtype, &pl)) {
-            const long long tab = align256((long long)P * sizeof(GnApplyProblem)), til = align256(pl.items * 8);
-            STORM_CHECK(off + tab + til <= blob_bytes && n < max_gops, "storm_program_group: table blob too small");
-            GnApplyProblem* t = reinterpret_cast<GnApplyProblem*>(host_blob + off);
-            GnFinItem* it = reinterpret_cast<GnFinItem*>(host_blob + off + tab);
-            const storm_op& o0 = ops[0][k];
-            long long ni = 0;
-            const void *gamma = nullptr, *beta = nullptr;
-            for (int g = 0; g < P; ++g) {
-                const storm_op& o = ops[g][k];
-                bool ok = true;
-                void* p[STORM_OP_NPTR];
-                for (int j = 0; j < STORM_OP_NPTR; ++j) p[j] = resolve(o.p[j], bufs[g], n_bufs, ok);
-                STORM_CHECK(ok, "storm_program_group: op %d of problem %d references a missing buffer", k, g);
-                // run_ops: GN_APPLY (xa, xb, stats, gamma, beta, out_act, out_raw; Ca, Cb, B, H, W, G, silu, resample; eps)
-                GnApplyProblem& q = t[g];
-                memset(&q, 0, sizeof(q));
-                q.xa = p[0]; q.xb = p[1]; q.stats = (const double*)p[2]; q.out_act = p[5]; q.out_raw = p[6]; q.H = (int)o.i[3]; q.W = (int)o.i[4];
-                gamma = p[3]; beta = p[4];
-                ni += gn_apply_group_problem((int)o0.i[7], (int)(o0.i[0] + o0.i[1]), (int)o.i[2], dtype, pl, g, q, it + ni);
-            }
-            STORM_CHECK(ni == pl.items, "storm_program_group: GroupNorm-apply items %lld != %lld", ni, pl.items);
-            GroupOp& go = gops[n++];
-            go.k = k; go.kind = 6; go.outC = (int)o0.i[0]; go.bn = (int)o0.i[1]; go.table_off = off; go.tiles_off = off + tab; go.ntiles = ni;
-            go.aux = gamma; go.aux2 = beta; go.faux = o0.f[0];
-            go.x[0] = (int)o0.i[5]; go.x[1] = (int)o0.i[7]; go.x[2] = (pl.rows_per_strip << 1) | (pl.share ? 1 : 0); go.x[3] = pl.max_cols;
-            off += tab + til;
-            continue;
-          } }
-        const bool narrow = narrow_candidate(ops, k, P, dtype), thin = !narrow && thin_candidate(ops, k, P, dtype);
-        if (!narrow && !thin && !group_candidate(ops, k, P, dtype)) continue;
-        long long t = 0;
-        for (int g = 0; g < P; ++g) {
-            bool ok = true;
-            void* p[STORM_OP_NPTR];
-            for (int j = 0; j < STORM_OP_NPTR; ++j) p[j] = resolve(ops[g][k].p[j], bufs[g], n_bufs, ok);
-            STORM_CHECK(ok, "storm_program_group: op %d of problem %d references a missing buffer", k, g);
-            conv_args_of(ops[g][k], p, dtype, args[(size_t)g]);
-            args[(size_t)g].splitk_ws = nullptr; args[(size_t)g].splitk_ws_bytes = 0;      // (a grouped launch never splits K)
-            t += narrow ? narrow_tiles(ops[g][k]) : op_tiles(ops[g][k]);
-        }
-        if (thin) {
-            const long long img = conv_thin_group_bytes(P);
-            STORM_CHECK(off + img <= blob_bytes && n < max_gops, "storm_program_group: table blob too small");
-            const long long nt = conv_thin_group_prepare(args.data(), P, host_blob + off);
-            if (nt <= 0) continue;
-            GroupOp& go = gops[n++];
-            go.k = k; go.kind = 3; go.outC = P; go.bn = args[0].seg[0].ntaps; go.table_off = off; go.tiles_off = off; go.ntiles = nt;
-            off += img;
-            continue;
-        }
-        if (narrow) {
-            const long long tabn = conv_narrow_group_bytes(P), tiln = align256(t * (long long)sizeof(pipe::GroupTile));
-            STORM_CHECK(off + tabn + tiln <= blob_bytes && n < max_gops, "storm_program_group: table blob too small");
-            const long long gotn = conv_narrow_group_prepare(args.data(), P, host_blob + off, reinterpret_cast<pipe::GroupTile*>(host_blob + off + tabn), t);
-            if (gotn != t) continue;
-            GroupOp& go = gops[n++];
-            go.k = k; go.kind = 2; go.outC = args[0].seg[0].Ca; go.bn = (args[0].seg[0].gn_ss != nullptr ? 2 : 0) | (args[0].seg[0].gn_silu ? 1 : 0);
-            go.table_off = off; go.tiles_off = off + tabn; go.ntiles = t;
-            off += tabn + tiln;
-            continue;
-        }
-        const long long tab = align256((long long)P * sizeof(pipe::PipeParams)), til = align256(t * (long long)sizeof(pipe::GroupTile));
-        STORM_CHECK(off + tab + til <= blob_bytes && n < max_gops, "storm_program_group: table blob too small");
-        const long long got = conv_pipe_group_prepare(args.data(), P, reinterpret_cast<pipe::PipeParams*>(host_blob + off),
-                                                      reinterpret_cast<pipe::GroupTile*>(host_blob + off + tab), t);
-        if (got != t) continue;                              // outside the pipelined kernel's coverage: runs problem by problem
-        GroupOp& go = gops[n++];
-        go.k = k; go.outC = args[0].outC; go.table_off = off; go.tiles_off = off + tab; go.ntiles = t;
-        go.bn = t * cdiv(args[0].outC, 256) >= 512 ? 256 : 128;   // the ladder's rule for the pipelined kernel's two tiles, on the GROUP's tile count
-        go.kind = 0;
-        off += tab + til;
+        GroupGeom geo;
+        const int kind = group_kind_of(ops, k, P, dtype, geo);
+        if (kind == GROUP_KINDS) continue;
+        STORM_CHECK(n < max_gops, "storm_program_group: more than %d grouped ops", max_gops);
+        STORM_CHECK(off + geo.table_bytes + geo.tiles_bytes <= blob_bytes, "storm_program_group: table blob too small");
+        GroupOp& go = gops[n];
+        go = GroupOp();
+        go.k = k; go.kind = (GroupKind)kind; go.table_off = off; go.tiles_off = off + geo.table_bytes; go.ntiles = geo.items;
+        const int rc = GROUP_TABLE[kind].fill(c, k, geo, host_blob + go.table_off, host_blob + go.tiles_off, go);
+        if (rc < 0) return rc;
+        if (rc == 0) continue;
+        ++n;
+        off += geo.table_bytes + geo.tiles_bytes;
     }
     return n;
 }
@@ -440,42 +419,7 @@ int storm::program_run_group(const storm_op* const* ops, int n_ops, void* const*
     for (int k = 0; k < n_ops; ++k) {
         if (gi < n_gops && gops[gi].k == k) {
             const GroupOp& go = gops[gi++];
-            if (go.kind == 6) {
-                GnApplyGroupPlan pl;
-                pl.rows_per_strip = go.x[2] >> 1; pl.share = go.x[2] & 1; pl.max_cols = go.x[3]; pl.items = go.ntiles;
-                if (int rc = launch_gn_apply_group(go.x[1], reinterpret_cast<const GnApplyProblem*>(dev_blob + go.table_off), dev_blob + go.tiles_off, pl, go.outC, go.bn, go.x[0],
-                                                   static_cast<const float*>(go.aux), static_cast<const float*>(go.aux2), go.faux, dtype, (hipStream_t)s)) return rc;
-                continue;
-            }
-            if (go.kind == 5) {
-                if (int rc = launch_attention_group(reinterpret_cast<const AttnProblem*>(dev_blob + go.table_off), reinterpret_cast<const AttnItem*>(dev_blob + go.tiles_off),
-                                                    (int)go.ntiles, static_cast<const float*>(go.aux), go.outC, go.faux, dtype, (hipStream_t)s)) return rc;
-                continue;
-            }
-            if (go.kind == 4) {
-                if (int rc = launch_fir_group(go.bn & 3, reinterpret_cast<const FirProblem*>(dev_blob + go.table_off), dev_blob + go.tiles_off, (int)go.ntiles, go.bn >> 2, go.outC,
-                                              dtype, (hipStream_t)s)) return rc;
-                continue;
-            }
-            if (go.kind == 3) {
-                if (int rc = launch_conv_thin_group(dev_blob + go.table_off, go.outC, go.ntiles, go.bn, dtype, (hipStream_t)s)) return rc;
-                continue;
-            }
-            if (go.kind == 2) {
-                storm_conv_args a0;
-                memset(&a0, 0, sizeof(a0));
-                a0.dtype = dtype; a0.seg[0].Ca = go.outC; a0.seg[0].gn_ss = (go.bn & 2) ? reinterpret_cast<const float*>(uintptr_t(16)) : nullptr; a0.seg[0].gn_silu = go.bn & 1;
-                if (int rc = launch_conv_narrow_group(a0, dev_blob + go.table_off, reinterpret_cast<const pipe::GroupTile*>(dev_blob + go.tiles_off), go.ntiles, (hipStream_t)s)) return rc;
-                continue;
-            }
-            if (go.kind == 1) {
-                if (int rc = launch_gn_finalize_group(reinterpret_cast<const GnFinProblem*>(dev_blob + go.table_off), dev_blob + go.tiles_off, (int)go.ntiles, go.outC,
-                                                      (hipStream_t)s)) return rc;
-                continue;
-            }
-            if (int rc = launch_conv_pipe_group(reinterpret_cast<const pipe::PipeParams*>(dev_blob + go.table_off),
-                                                reinterpret_cast<const pipe::GroupTile*>(dev_blob + go.tiles_off), go.ntiles, go.outC, go.bn, dtype,
-                                                (hipStream_t)s)) return rc;
+            if (int rc = GROUP_TABLE[go.kind].launch(go, dev_blob + go.table_off, dev_blob + go.tiles_off, dtype, (hipStream_t)s)) return rc;
             continue;
         }
         for (int g = 0; g < P; ++g) {
