@@ -551,15 +551,31 @@ int storm_tasnet_decode(const void* mask, const void* enc, const float* wd, floa
 
 /* ------------------------------------------------------------------------------------------
  * Program interpreter: runs a whole NCSN++ forward (or any op list) with one host call.
- * The op list is planned on the host side (storm_amd/backbones/plan.py) once per
+ * The op list is planned on the host side (csrc/ncsnpp_graph.hip) once per
  * (model, B, F, T, dtype); pointers are offsets into the caller-owned buffers in `bufs`.
  * Replaces the Python op-by-op dispatch of NCSNpp.forward (ncsnpp.py:281-450).
  * ------------------------------------------------------------------------------------------ */
+/* The slots of an op by code (csrc/op_fields.h names them; callers that read records by number - bench.py, tools/, tests/ - rely on them):
+ * a reference that is absent has buf < 0, an unused integer or float is 0. */
 enum {
-    STORM_OP_MEMSET = 0, STORM_OP_PACK_INPUT = 1, STORM_OP_TEMB = 2, STORM_OP_DENSE = 3,
-    STORM_OP_CONV = 4, STORM_OP_GN_STATS = 5, STORM_OP_GN_APPLY = 6, STORM_OP_FIR_UP = 7,
-    STORM_OP_FIR_DOWN = 8, STORM_OP_SOFTMAX = 9, STORM_OP_OUTPUT_HEAD = 10, STORM_OP_GN_FINALIZE = 11,
-    STORM_OP_ATTENTION = 12,
+    STORM_OP_MEMSET = 0,            /* p[0] dst; i = bytes (set to zero) */
+    STORM_OP_PACK_INPUT = 1,        /* p[0..2] complex inputs, p[3] out; i = n_in, B, F, T (storm_pack_input) */
+    STORM_OP_TEMB = 2,              /* p[0] t, p[1] gfp_W, p[2] W1, p[3] b1, p[4] W2, p[5] b2, p[6] act_temb; i = B, nf (storm_time_embedding) */
+    STORM_OP_DENSE = 3,             /* p[0] x, p[1] W, p[2] bias, p[3] out; i = B, N, K (storm_dense) */
+    STORM_OP_CONV = 4,              /* p[0..2] segment 0's src_a, src_b, w, p[3..5] segment 1's, p[6] out, p[7] bias, p[8] tbias, p[9] skip, p[10] gn_part,
+                                     * p[11] segment 0's gn_ss, p[12] split-K scratch; i = nseg, B, H, W, outC, Cout, tbias_stride, out_f32, then per segment
+                                     * (i[8..14], i[15..21]) Ca, Cb, CinP, w_rows, ntaps, w_bstride, w_tapstride, i[22] segment 0's bstride_a (< 0: H W Ca),
+                                     * i[23] out_bstride (< 0: H W outC); f = scale, segment 0's gn_silu, fp32 slabs in the scratch (storm_conv) */
+    STORM_OP_GN_STATS = 5,          /* p[0] xa, p[1] xb, p[2] stats; i = Ca, Cb, B, HW, groups (storm_gn_stats) */
+    STORM_OP_GN_APPLY = 6,          /* p[0] xa, p[1] xb, p[2] stats, p[3] gamma, p[4] beta, p[5] out_act, p[6] out_raw; i = Ca, Cb, B, H, W, groups, silu, resample;
+                                     * f = eps (storm_gn_apply) */
+    STORM_OP_FIR_UP = 7,            /* p[0] x, p[1] add, p[2] out; i = B, H, W, C (storm_fir_up2) */
+    STORM_OP_FIR_DOWN = 8,          /* p[0] x, p[1] out; i = B, H, W, C (storm_fir_down2) */
+    STORM_OP_SOFTMAX = 9,           /* p[0] scores, p[1] probs; i = rows, L, ld (storm_softmax_rows) */
+    STORM_OP_OUTPUT_HEAD = 10,      /* p[0] pyr, p[1] t, p[2] W, p[3] bias, p[4] out; i = cin, B, F, T, negate (storm_output_head) */
+    STORM_OP_GN_FINALIZE = 11,      /* p[0] part_a, p[1] part_b, p[2] stats, p[3] gamma, p[4] beta, p[5] ss; i = Ca, tiles_a, Cb, tiles_b, B, groups, count; f = eps
+                                     * (p[5] present: storm_gn_finalize_ss, else storm_gn_finalize, which reads neither gamma, beta, count nor eps) */
+    STORM_OP_ATTENTION = 12,        /* p[0] q, p[1] k, p[2] vT, p[3] bias, p[4] out, p[5] scratch; i = B, L, C, ldv, scratch_bytes; f = scale (storm_attention_ws) */
     STORM_OP_INPUT_PYRAMID = 13,    /* p[0..2] complex inputs (or none: level 0 is read), p[3..6] levels; i = n_in, B, F, T, n_levels, mean, centered */
     STORM_OP_OUTPUT_PYRAMID = 14,   /* p[0..7] ph (finest first), p[8] t, p[9] W, p[10] bias, p[11] out; i = cin, B, F, T, negate, n_levels */
     STORM_OP_COMBINE_CAT = 15       /* p[0] x, p[1] w, p[2] bias, p[3] h, p[4] out; i = npix, C, CinP (storm_combine_cat) */

@@ -204,6 +204,12 @@ struct PipeParams {
 struct GroupTile { unsigned int problem, b, yx, tile; };   // yx = ty0 | tx0 << 16; tile = index inside its problem (GroupNorm partials)
 }  // namespace pipe
 
+// defined in program.hip: storm_conv_args of a STORM_OP_CONV op.  conv_args_of: p = the op's STORM_OP_NPTR references resolved by the caller;
+// conv_shape_args_of: a placeholder non-NULL pointer for every reference the op has, for the questions that depend on shapes, dtype and which
+// optional pointers are present only (storm_conv_kernel_name, storm_conv_splitk_bytes)
+void conv_args_of(const storm_op& op, void* const* p, int dtype, storm_conv_args& a);
+void conv_shape_args_of(const storm_op& op, int dtype, storm_conv_args& a);
+
 // defined in conv_pipe.hip: software-pipelined 3x3 kernel (bf16 / fp16 operands), 256 output channels per workgroup
 bool conv_pipe_supports(const storm_conv_args& a);
 int launch_conv_pipe(const storm_conv_args& a, hipStream_t st);

@@ -23,9 +23,12 @@
 #include <cstdio>
 #include <cstring>
 #include "common.h"
+#include "conv_params.h"
+#include "op_fields.h"
 
 namespace storm {
 namespace graph {
+using namespace opf;
 
 constexpr long long ALIGN = 256;
 static inline long long up(long long x, long long m) { return (x + m - 1) / m * m; }
@@ -260,22 +263,23 @@ struct Program {
         const long long st = new_stats(G);
         if (xa.part >= 0 && (!xb || xb->part >= 0)) {
             storm_op& o = op(STORM_OP_GN_FINALIZE);
-            ws(o, 0, xa.part); if (xb) ws(o, 1, xb->part); ws(o, 2, st);
-            o.i[0] = xa.C; o.i[1] = xa.tiles; o.i[2] = xb ? xb->C : 0; o.i[3] = xb ? xb->tiles : 0; o.i[4] = B; o.i[5] = G;
+            ws(o, op_gnfin::PART_A, xa.part); if (xb) ws(o, op_gnfin::PART_B, xb->part); ws(o, op_gnfin::STATS, st);
+            o.i[op_gnfin::CA] = xa.C; o.i[op_gnfin::TILES_A] = xa.tiles; o.i[op_gnfin::CB] = xb ? xb->C : 0; o.i[op_gnfin::TILES_B] = xb ? xb->tiles : 0;
+            o.i[op_gnfin::B] = B; o.i[op_gnfin::G] = G;
         } else {
             storm_op& o = op(STORM_OP_GN_STATS);
-            ws(o, 0, xa.off); if (xb) ws(o, 1, xb->off); ws(o, 2, st);
-            o.i[0] = xa.C; o.i[1] = xb ? xb->C : 0; o.i[2] = B; o.i[3] = (long long)xa.H * xa.W; o.i[4] = G;
+            ws(o, op_gnstats::XA, xa.off); if (xb) ws(o, op_gnstats::XB, xb->off); ws(o, op_gnstats::STATS, st);
+            o.i[op_gnstats::CA] = xa.C; o.i[op_gnstats::CB] = xb ? xb->C : 0; o.i[op_gnstats::B] = B; o.i[op_gnstats::HW] = (long long)xa.H * xa.W; o.i[op_gnstats::G] = G;
         }
         const bool r_up = resample == 1 || resample == 3, r_dn = resample == 2 || resample == 4;      // (3 / 4: the non-FIR members, fir=False)
         const int OH = r_up ? 2 * xa.H : (r_dn ? xa.H / 2 : xa.H), OW = r_up ? 2 * xa.W : (r_dn ? xa.W / 2 : xa.W);
         Act out = new_act(OH, OW, Cc), raw;
         if (resample) raw = new_act(OH, OW, Cc);
         storm_op& o = op(STORM_OP_GN_APPLY);
-        ws(o, 0, xa.off); if (xb) ws(o, 1, xb->off); ws(o, 2, st); par(o, 3, wkey); par(o, 4, bkey); ws(o, 5, out.off);
-        if (raw.valid) ws(o, 6, raw.off);
-        o.i[0] = xa.C; o.i[1] = xb ? xb->C : 0; o.i[2] = B; o.i[3] = xa.H; o.i[4] = xa.W; o.i[5] = G; o.i[6] = silu; o.i[7] = resample;
-        o.f[0] = 1e-6f;
+        ws(o, op_gnapply::XA, xa.off); if (xb) ws(o, op_gnapply::XB, xb->off); ws(o, op_gnapply::STATS, st); par(o, op_gnapply::GAMMA, wkey); par(o, op_gnapply::BETA, bkey);
+        ws(o, op_gnapply::OUT_ACT, out.off); if (raw.valid) ws(o, op_gnapply::OUT_RAW, raw.off);
+        o.i[op_gnapply::CA] = xa.C; o.i[op_gnapply::CB] = xb ? xb->C : 0; o.i[op_gnapply::B] = B; o.i[op_gnapply::H] = xa.H; o.i[op_gnapply::W] = xa.W; o.i[op_gnapply::G] = G;
+        o.i[op_gnapply::SILU] = silu; o.i[op_gnapply::RESAMPLE] = resample; o.f[op_gnapply::EPS] = 1e-6f;
         return {out, raw};
     }
     // GroupNorm as a per-(batch, channel) affine table for a conv that fuses the apply (+SiLU) into its operand load
@@ -283,9 +287,9 @@ struct Program {
         const int Cc = xa.C + (xb ? xb->C : 0), G = std::min(Cc / 4, 32);
         const long long st = new_stats(G), ss = arena.alloc((long long)B * Cc * 2 * 4);
         storm_op& o = op(STORM_OP_GN_FINALIZE);
-        ws(o, 0, xa.part); if (xb) ws(o, 1, xb->part); ws(o, 2, st); par(o, 3, wkey); par(o, 4, bkey); ws(o, 5, ss);
-        o.i[0] = xa.C; o.i[1] = xa.tiles; o.i[2] = xb ? xb->C : 0; o.i[3] = xb ? xb->tiles : 0; o.i[4] = B; o.i[5] = G; o.i[6] = (long long)xa.H * xa.W;
-        o.f[0] = 1e-6f;
+        ws(o, op_gnfin::PART_A, xa.part); if (xb) ws(o, op_gnfin::PART_B, xb->part); ws(o, op_gnfin::STATS, st); par(o, op_gnfin::GAMMA, wkey); par(o, op_gnfin::BETA, bkey);
+        ws(o, op_gnfin::SS, ss); o.i[op_gnfin::CA] = xa.C; o.i[op_gnfin::TILES_A] = xa.tiles; o.i[op_gnfin::CB] = xb ? xb->C : 0; o.i[op_gnfin::TILES_B] = xb ? xb->tiles : 0;
+        o.i[op_gnfin::B] = B; o.i[op_gnfin::G] = G; o.i[op_gnfin::COUNT] = (long long)xa.H * xa.W; o.f[op_gnfin::EPS] = 1e-6f;
         return ss;
     }
     Seg wseg(const Act& a, const std::string& key, int taps, const Act* b = nullptr, long long gnss = -1) {
@@ -299,50 +303,39 @@ struct Program {
         const int outC = k.outC ? k.outC : (int)up(Cout, 8);
         Act out = new_act(H, W, outC, k.out_f32 ? 4 : 0);
         storm_op& o = op(STORM_OP_CONV);
-        o.i[0] = (long long)segs.size(); o.i[1] = B; o.i[2] = H; o.i[3] = W; o.i[4] = outC; o.i[5] = Cout; o.i[7] = k.out_f32;
-        for (size_t g = 0; g < segs.size(); ++g) {
-            const Seg& s = segs[g];
+        o.i[op_conv::NSEG] = (long long)segs.size(); o.i[op_conv::B] = B; o.i[op_conv::H] = H; o.i[op_conv::W] = W; o.i[op_conv::OUTC] = outC; o.i[op_conv::COUT] = Cout;
+        for (int g = 0; g < (int)segs.size(); ++g) {
+            const Seg& s = segs[(size_t)g];
             int Ca, Cb = 0;
-            if (s.a_is_act) { ws(o, 3 * (int)g, s.a.off); Ca = s.a.C; } else { ref(o, 3 * (int)g, s.a_buf, s.a_off); Ca = s.a_C; }
-            if (s.has_b) { ws(o, 3 * (int)g + 1, s.b.off); Cb = s.b.C; }
-            if (s.w_par) par(o, 3 * (int)g + 2, s.w_key); else ws(o, 3 * (int)g + 2, s.w_off);
-            const int q = 8 + 7 * (int)g;
-            o.i[q] = Ca; o.i[q + 1] = Cb; o.i[q + 2] = s.CinP; o.i[q + 3] = s.rows; o.i[q + 4] = s.taps; o.i[q + 5] = s.w_bstride;
-            o.i[q + 6] = s.w_tapstride >= 0 ? s.w_tapstride : (long long)s.CinP * s.rows;
+            if (s.a_is_act) { ws(o, op_conv::pseg(g, op_conv::SRC_A0), s.a.off); Ca = s.a.C; } else { ref(o, op_conv::pseg(g, op_conv::SRC_A0), s.a_buf, s.a_off); Ca = s.a_C; }
+            if (s.has_b) { ws(o, op_conv::pseg(g, op_conv::SRC_B0), s.b.off); Cb = s.b.C; }
+            if (s.w_par) par(o, op_conv::pseg(g, op_conv::W0), s.w_key); else ws(o, op_conv::pseg(g, op_conv::W0), s.w_off);
+            o.i[op_conv::iseg(g, op_conv::CA)] = Ca; o.i[op_conv::iseg(g, op_conv::CB)] = Cb; o.i[op_conv::iseg(g, op_conv::CINP)] = s.CinP; o.i[op_conv::iseg(g, op_conv::ROWS)] = s.rows;
+            o.i[op_conv::iseg(g, op_conv::TAPS)] = s.taps; o.i[op_conv::iseg(g, op_conv::W_BSTRIDE)] = s.w_bstride;
+            o.i[op_conv::iseg(g, op_conv::W_TAPSTRIDE)] = s.w_tapstride >= 0 ? s.w_tapstride : (long long)s.CinP * s.rows;
             flops += 2LL * B * H * W * Cout * (Ca + Cb) * s.taps;
         }
-        o.i[22] = k.src0_bstride; o.i[23] = k.out_bstride;
-        if (segs[0].gn >= 0) { ws(o, 11, segs[0].gn); o.f[1] = segs[0].gn_silu ? 1.0f : 0.0f; }
-        ws(o, 6, out.off);
-        if (!k.bias.empty()) par(o, 7, k.bias);
-        if (k.has_tb) { ref(o, 8, BUF_WS, k.tb_off); o.i[6] = k.tb_stride; }
-        if (k.skip) ws(o, 9, k.skip->off);
-        o.f[0] = k.scale;
+        o.i[op_conv::OUT_F32] = k.out_f32; o.i[op_conv::SRC0_BSTRIDE] = k.src0_bstride; o.i[op_conv::OUT_BSTRIDE] = k.out_bstride;
+        if (segs[0].gn >= 0) { ws(o, op_conv::GN_SS, segs[0].gn); o.f[op_conv::GN_SILU] = segs[0].gn_silu ? 1.0f : 0.0f; }
+        ws(o, op_conv::OUT, out.off);
+        if (!k.bias.empty()) par(o, op_conv::BIAS, k.bias);
+        if (k.has_tb) { ref(o, op_conv::TBIAS, BUF_WS, k.tb_off); o.i[op_conv::TBIAS_STRIDE] = k.tb_stride; }
+        if (k.skip) ws(o, op_conv::SKIP, k.skip->off);
+        o.f[op_conv::SCALE] = k.scale;
         if (k.want_part) {
             bool any9 = false; for (auto& s : segs) any9 = any9 || s.taps == 9;
             out.tiles = any9 ? ((W + 31) / 32) * ((H + 7) / 8) : (int)(((long long)H * W + 255) / 256);
             out.part = arena.alloc((long long)B * out.tiles * outC * 2 * 4);
-            ws(ops.back(), 10, out.part);
+            ws(o, op_conv::GN_PART, out.part);
         }
-        {   // few-tile 3x3 layers: scratch for storm_conv's split of K over workgroups - live for this op only (the stream orders
-            // every later writer of the region behind it)
-            storm_conv_args q;
-            memset(&q, 0, sizeof(q));
-            q.nseg = (int)segs.size(); q.B = B; q.H = H; q.W = W; q.outC = outC; q.Cout = Cout; q.out_f32 = k.out_f32; q.dtype = dtype;
-            for (size_t g = 0; g < segs.size(); ++g) {
-                const Seg& s = segs[g];
-                storm_conv_seg& sg = q.seg[g];
-                sg.src_a = &q; sg.w = &q;                       // (shape query: the pointers only have to be non-NULL)
-                sg.Ca = s.a_is_act ? s.a.C : s.a_C; sg.Cb = s.has_b ? s.b.C : 0; if (s.has_b) sg.src_b = &q;
-                sg.CinP = s.CinP; sg.w_rows = s.rows; sg.ntaps = s.taps; sg.w_bstride = s.w_bstride;
-                sg.w_tapstride = s.w_tapstride >= 0 ? s.w_tapstride : (long long)s.CinP * s.rows;
-                sg.bstride_a = (long long)H * W * sg.Ca; sg.bstride_b = (long long)H * W * sg.Cb;
-            }
-            const long long nb = storm_conv_splitk_bytes(&q);
-            if (nb > 0) {                                       // f[2] = the slabs the scratch holds (the interpreter sizes it from that)
-                const long long off = arena.alloc(nb); ws(ops.back(), 12, off); arena.release(off);
-                ops.back().f[2] = (float)(nb / ((long long)B * H * W * outC * 4));
-            }
+        // few-tile 3x3 layers: scratch for storm_conv's split of K over workgroups - live for this op only (the stream orders every later
+        // writer of the region behind it); the question is put to the op as it stands: every reference but the scratch's own is written
+        storm_conv_args q;
+        conv_shape_args_of(o, dtype, q);
+        const long long nb = storm_conv_splitk_bytes(&q);
+        if (nb > 0) {                                           // SPLITK_SLABS = the slabs the scratch holds (the interpreter sizes it from that)
+            const long long off = arena.alloc(nb); ws(o, op_conv::SPLITK_WS, off); arena.release(off);
+            o.f[op_conv::SPLITK_SLABS] = (float)(nb / ((long long)B * H * W * outC * 4));
         }
         return out;
     }
@@ -406,10 +399,10 @@ struct Program {
         if (fused_attention && storm_attention_supported(Cc, dtype)) {
             o = new_act(1, Lp, Cc);
             storm_op& a = op(STORM_OP_ATTENTION);
-            ws(a, 0, q.off); ws(a, 1, kk.off); ws(a, 2, vT.off); par(a, 3, k + "NIN_2.b"); ws(a, 4, o.off);
-            a.i[0] = B; a.i[1] = Lp; a.i[2] = Cc; a.i[3] = Lp8; a.f[0] = scale;
+            ws(a, op_attention::Q, q.off); ws(a, op_attention::K, kk.off); ws(a, op_attention::VT, vT.off); par(a, op_attention::BIAS, k + "NIN_2.b"); ws(a, op_attention::OUT, o.off);
+            a.i[op_attention::B] = B; a.i[op_attention::L] = Lp; a.i[op_attention::C] = Cc; a.i[op_attention::LDV] = Lp8; a.f[op_attention::SCALE] = scale;
             const long long nb = storm_attention_scratch_bytes(B, Lp, Cc, dtype);       // key-range split of small calls: scratch live for this op only
-            if (nb > 0) { const long long off = arena.alloc(nb); ws(ops.back(), 5, off); ops.back().i[4] = nb; arena.release(off); }
+            if (nb > 0) { const long long off = arena.alloc(nb); ws(a, op_attention::SCRATCH, off); a.i[op_attention::SCRATCH_BYTES] = nb; arena.release(off); }
             flops += 4LL * B * Lp * Lp * Cc;
             free_act(q); free_act(kk); free_act(vT);
         } else {
@@ -419,7 +412,7 @@ struct Program {
             free_act(q); free_act(kk);
             Act P = new_act(1, Lp, Lp8);
             storm_op& sm = op(STORM_OP_SOFTMAX);
-            ws(sm, 0, S.off); ws(sm, 1, P.off); sm.i[0] = (long long)B * Lp; sm.i[1] = Lp; sm.i[2] = Lp8;
+            ws(sm, op_softmax::SCORES, S.off); ws(sm, op_softmax::PROBS, P.off); sm.i[op_softmax::ROWS] = (long long)B * Lp; sm.i[op_softmax::L] = Lp; sm.i[op_softmax::LD] = Lp8;
             free_act(S);
             Seg sp; sp.a = P; sp.w_par = false; sp.w_off = vT.off; sp.CinP = Lp8; sp.rows = Cc; sp.taps = 1; sp.w_bstride = (long long)Cc * Lp8;
             ConvOpt co; co.bias = k + "NIN_2.b";
@@ -459,7 +452,7 @@ struct Program {
         for (auto& m : mods) n_gn += m.kind == RES ? 2 : (m.kind == ATTN || m.kind == GN ? 1 : 0);
         stats_bytes = n_gn * up((long long)B * 32 * 2 * 8, ALIGN);
         stats_off = arena.alloc(stats_bytes); stats_cursor = stats_off;
-        { storm_op& o = op(STORM_OP_MEMSET); ws(o, 0, stats_off); o.i[0] = stats_bytes; }
+        { storm_op& o = op(STORM_OP_MEMSET); ws(o, op_memset::DST, stats_off); o.i[op_memset::BYTES] = stats_bytes; }
         const int n_in = total / 2;
         // the input pyramid (input_skip): a function of the network input alone, so every level is built here, ahead of the U-Net - the packing and
         // up to three FIR x2 down steps per launch (csrc/pyramid.hip; `ncsnpp`: one launch, `ncsnpplarge` with its six steps: two)
@@ -470,20 +463,22 @@ struct Program {
         for (int l0 = 0; l0 == 0 || l0 < nlev - 1; l0 += 3) {
             const int nl = std::min(4, nlev - l0);
             storm_op& o = op(STORM_OP_INPUT_PYRAMID);
-            if (l0 == 0) for (int j = 0; j < n_in; ++j) ref(o, j, BUF_IN0 + j, 0);
-            for (int k = 0; k < nl; ++k) ws(o, 3 + k, ips[(size_t)(l0 + k)].off);
-            o.i[0] = l0 == 0 ? n_in : 0; o.i[1] = B; o.i[2] = F >> l0; o.i[3] = T >> l0; o.i[4] = nl; o.i[5] = cfg.fir ? 0 : 1; o.i[6] = cfg.centered ? 1 : 0;
+            if (l0 == 0) for (int j = 0; j < n_in; ++j) ref(o, op_inpyr::IN0 + j, BUF_IN0 + j, 0);
+            for (int k = 0; k < nl; ++k) ws(o, op_inpyr::LEVEL0 + k, ips[(size_t)(l0 + k)].off);
+            o.i[op_inpyr::N_IN] = l0 == 0 ? n_in : 0; o.i[op_inpyr::B] = B; o.i[op_inpyr::F] = F >> l0; o.i[op_inpyr::T] = T >> l0; o.i[op_inpyr::N_LEVELS] = nl;
+            o.i[op_inpyr::MEAN] = cfg.fir ? 0 : 1; o.i[op_inpyr::CENTERED] = cfg.centered ? 1 : 0;
         }
         Act x0 = ips[0];
         int midx = 1;
         if (cfg.conditional()) {
             const long long temb = arena.alloc((long long)B * 4 * cfg.nf * 4);
             storm_op& o = op(STORM_OP_TEMB);
-            ref(o, 0, BUF_T, 0); par(o, 1, "all_modules.0.W"); par(o, 2, "all_modules.1.weight"); par(o, 3, "all_modules.1.bias");
-            par(o, 4, "all_modules.2.weight"); par(o, 5, "all_modules.2.bias"); ws(o, 6, temb); o.i[0] = B; o.i[1] = cfg.nf;
+            ref(o, op_temb::TIME, BUF_T, 0); par(o, op_temb::GFP_W, "all_modules.0.W"); par(o, op_temb::W1, "all_modules.1.weight"); par(o, op_temb::B1, "all_modules.1.bias");
+            par(o, op_temb::W2, "all_modules.2.weight"); par(o, op_temb::B2, "all_modules.2.bias"); ws(o, op_temb::OUT, temb); o.i[op_temb::B] = B; o.i[op_temb::NF] = cfg.nf;
             dense_out = arena.alloc((long long)B * lay.dense_rows * 4);
             storm_op& d = op(STORM_OP_DENSE);
-            ws(d, 0, temb); par(d, 1, "dense.weight"); par(d, 2, "dense.bias"); ws(d, 3, dense_out); d.i[0] = B; d.i[1] = lay.dense_rows; d.i[2] = 4 * cfg.nf;
+            ws(d, op_dense::X, temb); par(d, op_dense::W, "dense.weight"); par(d, op_dense::BIAS, "dense.bias"); ws(d, op_dense::OUT, dense_out);
+            d.i[op_dense::B] = B; d.i[op_dense::N] = lay.dense_rows; d.i[op_dense::K] = 4 * cfg.nf;
             midx = 3;
         }
         Act ip = x0;
@@ -506,8 +501,8 @@ struct Program {
                     const Entry& e = lay.at(kk + "Conv_0.weight");
                     hc = new_act(h.H, h.W, 2 * h.C);
                     storm_op& o = op(STORM_OP_COMBINE_CAT);
-                    ws(o, 0, ip.off); par(o, 1, kk + "Conv_0.weight"); par(o, 2, kk + "Conv_0.bias"); ws(o, 3, h.off); ws(o, 4, hc.off);
-                    o.i[0] = (long long)B * h.H * h.W; o.i[1] = h.C; o.i[2] = e.shape[2];
+                    ws(o, op_combine::X, ip.off); par(o, op_combine::W, kk + "Conv_0.weight"); par(o, op_combine::BIAS, kk + "Conv_0.bias"); ws(o, op_combine::H, h.off);
+                    ws(o, op_combine::OUT, hc.off); o.i[op_combine::NPIX] = (long long)B * h.H * h.W; o.i[op_combine::C] = h.C; o.i[op_combine::CINP] = e.shape[2];
                     flops += 2LL * B * h.H * h.W * h.C * total;
                 } else {
                     ConvOpt c; c.bias = kk + "Conv_0.bias"; c.skip = &h; c.want_part = fuse_stats;
@@ -544,10 +539,10 @@ struct Program {
         // progressive='none': the same launch over the one level there is
         const int npl = (int)phs.size();
         storm_op& o = op(STORM_OP_OUTPUT_PYRAMID);
-        for (int k = 0; k < npl; ++k) ws(o, k, phs[(size_t)(npl - 1 - k)].off);
-        if (cfg.scale_by_sigma()) ref(o, 8, BUF_T, 0);
-        par(o, 9, "output_layer.weight"); par(o, 10, "output_layer.bias"); ref(o, 11, BUF_OUT, 0);
-        o.i[0] = total; o.i[1] = B; o.i[2] = F; o.i[3] = T; o.i[4] = 0; o.i[5] = npl;
+        for (int k = 0; k < npl; ++k) ws(o, op_outpyr::PH0 + k, phs[(size_t)(npl - 1 - k)].off);
+        if (cfg.scale_by_sigma()) ref(o, op_outpyr::TIME, BUF_T, 0);
+        par(o, op_outpyr::W, "output_layer.weight"); par(o, op_outpyr::BIAS, "output_layer.bias"); ref(o, op_outpyr::OUT, BUF_OUT, 0);
+        o.i[op_outpyr::CIN] = total; o.i[op_outpyr::B] = B; o.i[op_outpyr::F] = F; o.i[op_outpyr::T] = T; o.i[op_outpyr::NEGATE] = 0; o.i[op_outpyr::N_LEVELS] = npl;
         for (const Act& a : phs) free_act(a);
         ws_bytes = arena.top;
         return STORM_OK;
@@ -831,7 +826,7 @@ static int run_range(const Program& p, int a, int b, void* const* bufs, int dtyp
     if (be > a) if (int rc = storm_program_run(p.ops.data() + a, be - a, bufs, N_BUFS, dtype, s)) return rc;
     if (b == n && a < n) {
         storm_op head = p.ops[n - 1];
-        head.i[4] = negate ? 1 : 0;
+        head.i[op_outpyr::NEGATE] = negate ? 1 : 0;
         return storm_program_run(&head, 1, bufs, N_BUFS, dtype, s);
     }
     return STORM_OK;

@@ -1,12 +1,14 @@
 // Program interpreter: executes a host-planned op list (one NCSN++ forward) with a single
 // C-ABI call, so the ~300 kernel launches of a score evaluation cost no Python dispatch.
-// Field conventions are mirrored by storm_amd/backbones/plan.py (class Op).
+// The slots of an op are named by op_fields.h; the Python mirror of the record is storm_amd/_lib.py (class Op).
 #include <cstring>
 #include <vector>
 #include "common.h"
 #include "conv_params.h"
+#include "op_fields.h"
 
 using namespace storm;
+using namespace storm::opf;
 
 // the STORM_OP_NPTR references of an op against one problem's buffers (g: the problem of a grouped evaluation, < 0 = storm_program_run's own list)
 static int resolve_op(const storm_op& op, void* const* bufs, int n_bufs, int k, int g, void** p) {
@@ -23,34 +25,38 @@ static int resolve_op(const storm_op& op, void* const* bufs, int n_bufs, int k, 
     return STORM_OK;
 }
 
-// storm_conv_args of a STORM_OP_CONV op (pointers resolved by the caller; NULL pointers when only the shape matters)
-static void conv_args_of(const storm_op& op, void* const* p, int dtype, storm_conv_args& a) {
+void storm::conv_args_of(const storm_op& op, void* const* p, int dtype, storm_conv_args& a) {
+    using namespace op_conv;
     const int64_t* i = op.i;
     memset(&a, 0, sizeof(a));
-    a.nseg = (int)i[0]; a.B = (int)i[1]; a.H = (int)i[2]; a.W = (int)i[3];
-    a.outC = (int)i[4]; a.Cout = (int)i[5]; a.tbias_stride = (int)i[6]; a.out_f32 = (int)i[7];
+    a.nseg = (int)i[NSEG]; a.B = (int)i[B]; a.H = (int)i[H]; a.W = (int)i[W];
+    a.outC = (int)i[OUTC]; a.Cout = (int)i[COUT]; a.tbias_stride = (int)i[TBIAS_STRIDE]; a.out_f32 = (int)i[OUT_F32];
     const long long hw = (long long)a.H * a.W;
     for (int g = 0; g < 2; ++g) {
         storm_conv_seg& sgm = a.seg[g];
-        const int64_t* q = i + 8 + 7 * g;
-        sgm.src_a = p[3 * g]; sgm.src_b = p[3 * g + 1]; sgm.w = p[3 * g + 2];
-        sgm.Ca = (int)q[0]; sgm.Cb = (int)q[1]; sgm.CinP = (int)q[2]; sgm.w_rows = (int)q[3];
-        sgm.ntaps = (int)q[4]; sgm.w_bstride = q[5]; sgm.w_tapstride = q[6];
+        sgm.src_a = p[pseg(g, SRC_A0)]; sgm.src_b = p[pseg(g, SRC_B0)]; sgm.w = p[pseg(g, W0)];
+        sgm.Ca = (int)i[iseg(g, CA)]; sgm.Cb = (int)i[iseg(g, CB)]; sgm.CinP = (int)i[iseg(g, CINP)]; sgm.w_rows = (int)i[iseg(g, ROWS)];
+        sgm.ntaps = (int)i[iseg(g, TAPS)]; sgm.w_bstride = i[iseg(g, W_BSTRIDE)]; sgm.w_tapstride = i[iseg(g, W_TAPSTRIDE)];
         sgm.bstride_a = hw * sgm.Ca; sgm.bstride_b = hw * sgm.Cb;
     }
-    if (i[22] >= 0) a.seg[0].bstride_a = i[22];
-    a.out = p[6]; a.bias = (const float*)p[7]; a.tbias = (const float*)p[8]; a.skip = p[9];
-    a.out_bstride = i[23] >= 0 ? i[23] : hw * a.outC;
+    if (i[SRC0_BSTRIDE] >= 0) a.seg[0].bstride_a = i[SRC0_BSTRIDE];
+    a.out = p[OUT]; a.bias = (const float*)p[BIAS]; a.tbias = (const float*)p[TBIAS]; a.skip = p[SKIP];
+    a.out_bstride = i[OUT_BSTRIDE] >= 0 ? i[OUT_BSTRIDE] : hw * a.outC;
     a.skip_bstride = hw * a.outC;
-    a.scale = op.f[0];
+    a.scale = op.f[SCALE];
     a.dtype = dtype;
-    a.gn_part = (float*)p[10];
-    a.seg[0].gn_ss = (const float*)p[11];
-    a.seg[0].gn_silu = op.f[1] != 0.f;
-    if (p[12] != nullptr) {                                 // split-K scratch: f[2] fp32 slabs [B][H][W][outC] (storm_conv_splitk_bytes at plan time)
-        a.splitk_ws = p[12];
-        a.splitk_ws_bytes = (long long)op.f[2] * a.B * hw * a.outC * 4;
+    a.gn_part = (float*)p[GN_PART];
+    a.seg[0].gn_ss = (const float*)p[GN_SS];
+    a.seg[0].gn_silu = op.f[GN_SILU] != 0.f;
+    if (p[SPLITK_WS] != nullptr) {                          // split-K scratch: SPLITK_SLABS fp32 slabs [B][H][W][outC] (storm_conv_splitk_bytes at plan time)
+        a.splitk_ws = p[SPLITK_WS];
+        a.splitk_ws_bytes = (long long)op.f[SPLITK_SLABS] * a.B * hw * a.outC * 4;
     }
+}
+void storm::conv_shape_args_of(const storm_op& op, int dtype, storm_conv_args& a) {
+    void* p[STORM_OP_NPTR];
+    for (int j = 0; j < STORM_OP_NPTR; ++j) p[j] = op.p[j].buf >= 0 ? reinterpret_cast<void*>(uintptr_t(16)) : nullptr;
+    conv_args_of(op, p, dtype, a);
 }
 
 static int run_ops(const storm_op* ops, int n_ops, void* const* bufs, int n_bufs, int dtype, storm_stream_t s,
@@ -64,76 +70,72 @@ static int run_ops(const storm_op* ops, int n_ops, void* const* bufs, int n_bufs
         if (int rc = resolve_op(op, bufs, n_bufs, k, -1, p)) return rc;
         const int64_t* i = op.i;
         int rc = STORM_OK;
-        switch (op.code) {
-            case STORM_OP_MEMSET:
-                STORM_HIP(hipMemsetAsync(p[0], 0, (size_t)i[0], st));
-                break;
-            case STORM_OP_PACK_INPUT: {
-                const float* in[3] = {(const float*)p[0], (const float*)p[1], (const float*)p[2]};
-                rc = storm_pack_input(in, (int)i[0], p[3], (int)i[1], (int)i[2], (int)i[3], dtype, s);
-                break;
-            }
-            case STORM_OP_TEMB:
-                rc = storm_time_embedding((const float*)p[0], (const float*)p[1], (const float*)p[2], (const float*)p[3],
-                                          (const float*)p[4], (const float*)p[5], (float*)p[6], (int)i[0], (int)i[1], s);
-                break;
-            case STORM_OP_DENSE:
-                rc = storm_dense((const float*)p[0], (const float*)p[1], (const float*)p[2], (float*)p[3], (int)i[0],
-                                 (int)i[1], (int)i[2], s);
-                break;
+        switch (op.code) {                                   // (each case names its op's slots by its namespace of op_fields.h)
+            case STORM_OP_MEMSET: { using namespace op_memset;
+                STORM_HIP(hipMemsetAsync(p[DST], 0, (size_t)i[BYTES], st));
+                break; }
+            case STORM_OP_PACK_INPUT: { using namespace op_pack;
+                const float* in[3] = {(const float*)p[IN0], (const float*)p[IN0 + 1], (const float*)p[IN0 + 2]};
+                rc = storm_pack_input(in, (int)i[N_IN], p[OUT], (int)i[B], (int)i[F], (int)i[T], dtype, s);
+                break; }
+            case STORM_OP_TEMB: { using namespace op_temb;
+                rc = storm_time_embedding((const float*)p[TIME], (const float*)p[GFP_W], (const float*)p[W1], (const float*)p[B1], (const float*)p[W2],
+                                          (const float*)p[B2], (float*)p[OUT], (int)i[B], (int)i[NF], s);
+                break; }
+            case STORM_OP_DENSE: { using namespace op_dense;
+                rc = storm_dense((const float*)p[X], (const float*)p[W], (const float*)p[BIAS], (float*)p[OUT], (int)i[B], (int)i[N], (int)i[K], s);
+                break; }
             case STORM_OP_CONV: {
                 storm_conv_args a;
                 conv_args_of(op, p, dtype, a);
                 rc = storm_conv(&a, s);
-                break;
-            }
-            case STORM_OP_GN_STATS:
-                rc = storm_gn_stats(p[0], (int)i[0], p[1], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (double*)p[2], dtype, s);
-                break;
-            case STORM_OP_GN_FINALIZE:
-                if (p[5] != nullptr)
-                    rc = storm_gn_finalize_ss((const float*)p[0], (int)i[0], (int)i[1], (const float*)p[1], (int)i[2], (int)i[3],
-                                              (int)i[4], (int)i[5], (long long)i[6], (const float*)p[3], (const float*)p[4],
-                                              op.f[0], (double*)p[2], (float*)p[5], s);
+                break; }
+            case STORM_OP_GN_STATS: { using namespace op_gnstats;
+                rc = storm_gn_stats(p[XA], (int)i[CA], p[XB], (int)i[CB], (int)i[B], (int)i[HW], (int)i[G], (double*)p[STATS], dtype, s);
+                break; }
+            case STORM_OP_GN_FINALIZE: { using namespace op_gnfin;
+                if (p[SS] != nullptr)
+                    rc = storm_gn_finalize_ss((const float*)p[PART_A], (int)i[CA], (int)i[TILES_A], (const float*)p[PART_B], (int)i[CB], (int)i[TILES_B],
+                                              (int)i[B], (int)i[G], (long long)i[COUNT], (const float*)p[GAMMA], (const float*)p[BETA],
+                                              op.f[EPS], (double*)p[STATS], (float*)p[SS], s);
                 else
-                    rc = storm_gn_finalize((const float*)p[0], (int)i[0], (int)i[1], (const float*)p[1], (int)i[2], (int)i[3],
-                                           (int)i[4], (int)i[5], (double*)p[2], s);
-                break;
-            case STORM_OP_GN_APPLY:
-                rc = storm_gn_apply(p[0], (int)i[0], p[1], (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int)i[5],
-                                    (const double*)p[2], (const float*)p[3], (const float*)p[4], op.f[0], (int)i[6],
-                                    (int)i[7], p[5], p[6], dtype, s);
-                break;
-            case STORM_OP_FIR_UP:
-                rc = storm_fir_up2(p[0], p[1], p[2], (int)i[0], (int)i[1], (int)i[2], (int)i[3], dtype, s);
-                break;
-            case STORM_OP_FIR_DOWN:
-                rc = storm_fir_down2(p[0], p[1], (int)i[0], (int)i[1], (int)i[2], (int)i[3], dtype, s);
-                break;
-            case STORM_OP_SOFTMAX:
-                rc = storm_softmax_rows((const float*)p[0], p[1], (long long)i[0], (int)i[1], (int)i[2], dtype, s);
-                break;
-            case STORM_OP_ATTENTION:
-                rc = storm_attention_ws(p[0], p[1], p[2], (const float*)p[3], p[4], (int)i[0], (int)i[1], (int)i[2], (int)i[3],
-                                        (long long)i[1] * i[2], (long long)i[1] * i[2], (long long)i[2] * i[3], (long long)i[1] * i[2],
-                                        op.f[0], dtype, p[5], (long long)i[4], s);
-                break;
-            case STORM_OP_OUTPUT_HEAD:
-                rc = storm_output_head(p[0], (const float*)p[1], (const float*)p[2], (const float*)p[3], (int)i[0],
-                                       (float*)p[4], (int)i[1], (int)i[2], (int)i[3], (int)i[4], dtype, s);
-                break;
-            case STORM_OP_INPUT_PYRAMID: {
-                const float* in[3] = {(const float*)p[0], (const float*)p[1], (const float*)p[2]};
-                rc = storm_input_pyramid_ex(i[0] > 0 ? in : nullptr, (int)i[0], p + 3, (int)i[4], (int)i[1], (int)i[2], (int)i[3], (int)i[5], (int)i[6], dtype, s);
-                break;
-            }
-            case STORM_OP_OUTPUT_PYRAMID:
-                rc = storm_output_pyramid(p, (int)i[5], (const float*)p[8], (const float*)p[9], (const float*)p[10], (int)i[0],
-                                          (float*)p[11], (int)i[1], (int)i[2], (int)i[3], (int)i[4], dtype, s);
-                break;
-            case STORM_OP_COMBINE_CAT:
-                rc = storm_combine_cat(p[0], p[1], (int)i[2], (const float*)p[2], p[3], p[4], (long long)i[0], (int)i[1], dtype, s);
-                break;
+                    rc = storm_gn_finalize((const float*)p[PART_A], (int)i[CA], (int)i[TILES_A], (const float*)p[PART_B], (int)i[CB], (int)i[TILES_B],
+                                           (int)i[B], (int)i[G], (double*)p[STATS], s);
+                break; }
+            case STORM_OP_GN_APPLY: { using namespace op_gnapply;
+                rc = storm_gn_apply(p[XA], (int)i[CA], p[XB], (int)i[CB], (int)i[B], (int)i[H], (int)i[W], (int)i[G],
+                                    (const double*)p[STATS], (const float*)p[GAMMA], (const float*)p[BETA], op.f[EPS], (int)i[SILU],
+                                    (int)i[RESAMPLE], p[OUT_ACT], p[OUT_RAW], dtype, s);
+                break; }
+            case STORM_OP_FIR_UP: { using namespace op_firup;
+                rc = storm_fir_up2(p[X], p[ADD], p[OUT], (int)i[B], (int)i[H], (int)i[W], (int)i[C], dtype, s);
+                break; }
+            case STORM_OP_FIR_DOWN: { using namespace op_firdown;
+                rc = storm_fir_down2(p[X], p[OUT], (int)i[B], (int)i[H], (int)i[W], (int)i[C], dtype, s);
+                break; }
+            case STORM_OP_SOFTMAX: { using namespace op_softmax;
+                rc = storm_softmax_rows((const float*)p[SCORES], p[PROBS], (long long)i[ROWS], (int)i[L], (int)i[LD], dtype, s);
+                break; }
+            case STORM_OP_ATTENTION: { using namespace op_attention;
+                rc = storm_attention_ws(p[Q], p[K], p[VT], (const float*)p[BIAS], p[OUT], (int)i[B], (int)i[L], (int)i[C], (int)i[LDV],
+                                        (long long)i[L] * i[C], (long long)i[L] * i[C], (long long)i[C] * i[LDV], (long long)i[L] * i[C],
+                                        op.f[SCALE], dtype, p[SCRATCH], (long long)i[SCRATCH_BYTES], s);
+                break; }
+            case STORM_OP_OUTPUT_HEAD: { using namespace op_head;
+                rc = storm_output_head(p[PYR], (const float*)p[TIME], (const float*)p[W], (const float*)p[BIAS], (int)i[CIN],
+                                       (float*)p[OUT], (int)i[B], (int)i[F], (int)i[T], (int)i[NEGATE], dtype, s);
+                break; }
+            case STORM_OP_INPUT_PYRAMID: { using namespace op_inpyr;
+                const float* in[3] = {(const float*)p[IN0], (const float*)p[IN0 + 1], (const float*)p[IN0 + 2]};
+                rc = storm_input_pyramid_ex(i[N_IN] > 0 ? in : nullptr, (int)i[N_IN], p + LEVEL0, (int)i[N_LEVELS], (int)i[B], (int)i[F], (int)i[T], (int)i[MEAN], (int)i[CENTERED], dtype, s);
+                break; }
+            case STORM_OP_OUTPUT_PYRAMID: { using namespace op_outpyr;
+                rc = storm_output_pyramid(p + PH0, (int)i[N_LEVELS], (const float*)p[TIME], (const float*)p[W], (const float*)p[BIAS], (int)i[CIN],
+                                          (float*)p[OUT], (int)i[B], (int)i[F], (int)i[T], (int)i[NEGATE], dtype, s);
+                break; }
+            case STORM_OP_COMBINE_CAT: { using namespace op_combine;
+                rc = storm_combine_cat(p[X], p[W], (int)i[CINP], (const float*)p[BIAS], p[H], p[OUT], (long long)i[NPIX], (int)i[C], dtype, s);
+                break; }
             default:
                 STORM_CHECK(false, "storm_program_run: op %d has unknown code %d", k, op.code);
         }
@@ -162,20 +164,21 @@ struct GroupDesc {
 long long align256(long long v) { return (v + 255) / 256 * 256; }
 bool is16(int dtype) { return dtype == STORM_BF16 || dtype == STORM_F16; }
 
-// -- fused attention of the bottleneck: STORM_OP_ATTENTION (q, k, vT, bias, out, scratch; B, L, C, ldv; scale), same channels and scale in every problem
+// -- fused attention of the bottleneck (STORM_OP_ATTENTION): same channels and scale in every problem
 bool attn_match(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo) {
     const storm_op& o0 = ops[0][k];
-    if (o0.code != STORM_OP_ATTENTION || !attn_group_supported((int)o0.i[2], dtype)) return false;
+    if (o0.code != STORM_OP_ATTENTION || !attn_group_supported((int)o0.i[op_attention::C], dtype)) return false;
     geo.items = 0;
     for (int g = 0; g < P; ++g) {
         const storm_op& o = ops[g][k];
-        if (o.code != STORM_OP_ATTENTION || o.i[2] != o0.i[2] || o.f[0] != o0.f[0]) return false;
-        geo.items += attn_group_items((int)o.i[0], (int)o.i[1]);
+        if (o.code != STORM_OP_ATTENTION || o.i[op_attention::C] != o0.i[op_attention::C] || o.f[op_attention::SCALE] != o0.f[op_attention::SCALE]) return false;
+        geo.items += attn_group_items((int)o.i[op_attention::B], (int)o.i[op_attention::L]);
     }
     geo.table_bytes = attn_group_table_bytes(P); geo.tiles_bytes = align256(geo.items * (long long)sizeof(AttnItem));
     return geo.items < (1LL << 31);                          // (the launch's grid.x)
 }
 int attn_fill(GroupCtx& c, int k, const GroupGeom&, char* table, char* tiles, GroupOp& go) {
+    using namespace op_attention;
     AttnProblem* t = reinterpret_cast<AttnProblem*>(table);
     AttnItem* it = reinterpret_cast<AttnItem*>(tiles);
     long long ni = 0;
@@ -183,9 +186,9 @@ int attn_fill(GroupCtx& c, int k, const GroupGeom&, char* table, char* tiles, Gr
     for (int g = 0; g < c.P; ++g) {
         const storm_op& o = c.ops[g][k];
         if (int rc = resolve_op(o, c.bufs[g], c.n_bufs, k, g, p)) return rc;
-        ni += attn_group_problem(g, p[0], p[1], p[2], p[4], (int)o.i[0], (int)o.i[1], (int)o.i[2], (int)o.i[3], t[g], it + ni);
+        ni += attn_group_problem(g, p[Q], p[K], p[VT], p[OUT], (int)o.i[B], (int)o.i[L], (int)o.i[C], (int)o.i[LDV], t[g], it + ni);
     }
-    go.attention.C = (int)c.ops[0][k].i[2]; go.attention.bias = static_cast<const float*>(p[3]); go.attention.scale = c.ops[0][k].f[0];
+    go.attention.C = (int)c.ops[0][k].i[C]; go.attention.bias = static_cast<const float*>(p[BIAS]); go.attention.scale = c.ops[0][k].f[SCALE];
     return 1;
 }
 int attn_launch(const GroupOp& go, const char* dev_table, const char* dev_tiles, int dtype, hipStream_t st) {
@@ -199,28 +202,28 @@ bool fin_match(const storm_op* const* ops, int k, int P, int, GroupGeom& geo) {
     geo.items = 0;
     for (int g = 0; g < P; ++g) {
         const storm_op& o = ops[g][k];
-        if (o.code != STORM_OP_GN_FINALIZE || o.i[5] != o0.i[5] || o.i[0] + o.i[2] != o0.i[0] + o0.i[2]) return false;
-        geo.items += o.i[4];
+        if (o.code != STORM_OP_GN_FINALIZE || o.i[op_gnfin::G] != o0.i[op_gnfin::G] || o.i[op_gnfin::CA] + o.i[op_gnfin::CB] != o0.i[op_gnfin::CA] + o0.i[op_gnfin::CB]) return false;
+        geo.items += o.i[op_gnfin::B];
     }
     geo.table_bytes = align256((long long)P * sizeof(GnFinProblem)); geo.tiles_bytes = align256(geo.items * (long long)sizeof(GnFinItem));
     return geo.items < 65536;                                // (the launch's grid.y)
 }
 int fin_fill(GroupCtx& c, int k, const GroupGeom&, char* table, char* tiles, GroupOp& go) {
+    using namespace op_gnfin;
     GnFinProblem* t = reinterpret_cast<GnFinProblem*>(table);
     GnFinItem* it = reinterpret_cast<GnFinItem*>(tiles);
     for (int g = 0; g < c.P; ++g) {
         const storm_op& o = c.ops[g][k];
         void* p[STORM_OP_NPTR];
         if (int rc = resolve_op(o, c.bufs[g], c.n_bufs, k, g, p)) return rc;
-        // run_ops: GN_FINALIZE (pa, pb, stats, gamma, beta, ss; Ca, tiles_a, Cb, tiles_b, B, G, count; eps)
         GnFinProblem& q = t[g];
         memset(&q, 0, sizeof(q));
-        q.pa = (const float*)p[0]; q.pb = (const float*)p[1]; q.stats = (double*)p[2]; q.gamma = (const float*)p[3]; q.beta = (const float*)p[4];
-        q.ss = (float*)p[5]; q.count = p[5] != nullptr ? (long long)o.i[6] : 0; q.Ca = (int)o.i[0]; q.tiles_a = (int)o.i[1]; q.Cb = (int)o.i[2];
-        q.tiles_b = (int)o.i[3]; q.eps = p[5] != nullptr ? o.f[0] : 0.f;
-        for (int b = 0; b < (int)o.i[4]; ++b) { it->problem = g; it->b = b; ++it; }
+        q.pa = (const float*)p[PART_A]; q.pb = (const float*)p[PART_B]; q.stats = (double*)p[STATS]; q.gamma = (const float*)p[GAMMA]; q.beta = (const float*)p[BETA];
+        q.ss = (float*)p[SS]; q.count = p[SS] != nullptr ? (long long)o.i[COUNT] : 0; q.Ca = (int)o.i[CA]; q.tiles_a = (int)o.i[TILES_A]; q.Cb = (int)o.i[CB];
+        q.tiles_b = (int)o.i[TILES_B]; q.eps = p[SS] != nullptr ? o.f[EPS] : 0.f;
+        for (int b = 0; b < (int)o.i[B]; ++b) { it->problem = g; it->b = b; ++it; }
     }
-    go.finalize.groups = (int)c.ops[0][k].i[5];
+    go.finalize.groups = (int)c.ops[0][k].i[G];
     return 1;
 }
 int fin_launch(const GroupOp& go, const char* dev_table, const char* dev_tiles, int, hipStream_t st) {
@@ -230,21 +233,23 @@ int fin_launch(const GroupOp& go, const char* dev_table, const char* dev_tiles, 
 // -- GroupNorm-apply + SiLU + FIR x2 of h and x (the up / down resblocks' first op: STORM_OP_GN_APPLY with resample 1 / 2): same channels, groups and
 // affine parameters in every problem
 bool apply_match(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo) {
+    using namespace op_gnapply;
     const storm_op& o0 = ops[0][k];
-    if (!is16(dtype) || o0.code != STORM_OP_GN_APPLY || (o0.i[7] != 1 && o0.i[7] != 2) || o0.i[6] == 0 || P > 64) return false;
-    int B[64], H[64], W[64];
+    if (!is16(dtype) || o0.code != STORM_OP_GN_APPLY || (o0.i[RESAMPLE] != 1 && o0.i[RESAMPLE] != 2) || o0.i[SILU] == 0 || P > 64) return false;
+    int Bs[64], Hs[64], Ws[64];
     for (int g = 0; g < P; ++g) {
         const storm_op& o = ops[g][k];
-        if (o.code != STORM_OP_GN_APPLY || o.i[0] != o0.i[0] || o.i[1] != o0.i[1] || o.i[5] != o0.i[5] || o.i[6] != o0.i[6] || o.i[7] != o0.i[7] || o.f[0] != o0.f[0]) return false;
-        if (o.p[6].buf < 0) return false;                    // (the resampling form always writes both tensors)
-        B[g] = (int)o.i[2]; H[g] = (int)o.i[3]; W[g] = (int)o.i[4];
+        if (o.code != STORM_OP_GN_APPLY || o.i[CA] != o0.i[CA] || o.i[CB] != o0.i[CB] || o.i[G] != o0.i[G] || o.i[SILU] != o0.i[SILU] || o.i[RESAMPLE] != o0.i[RESAMPLE] || o.f[EPS] != o0.f[EPS]) return false;
+        if (o.p[OUT_RAW].buf < 0) return false;              // (the resampling form always writes both tensors)
+        Bs[g] = (int)o.i[B]; Hs[g] = (int)o.i[H]; Ws[g] = (int)o.i[W];
     }
-    if (!gn_apply_group_plan((int)o0.i[7], (int)(o0.i[0] + o0.i[1]), P, B, H, W, dtype, geo.apply)) return false;
+    if (!gn_apply_group_plan((int)o0.i[RESAMPLE], (int)(o0.i[CA] + o0.i[CB]), P, Bs, Hs, Ws, dtype, geo.apply)) return false;
     geo.items = geo.apply.items;
     geo.table_bytes = align256((long long)P * sizeof(GnApplyProblem)); geo.tiles_bytes = align256(geo.items * (long long)sizeof(GnFinItem));
     return true;
 }
 int apply_fill(GroupCtx& c, int k, const GroupGeom& geo, char* table, char* tiles, GroupOp& go) {
+    using namespace op_gnapply;
     GnApplyProblem* t = reinterpret_cast<GnApplyProblem*>(table);
     GnFinItem* it = reinterpret_cast<GnFinItem*>(tiles);
     const storm_op& o0 = c.ops[0][k];
@@ -253,15 +258,14 @@ int apply_fill(GroupCtx& c, int k, const GroupGeom& geo, char* table, char* tile
     for (int g = 0; g < c.P; ++g) {
         const storm_op& o = c.ops[g][k];
         if (int rc = resolve_op(o, c.bufs[g], c.n_bufs, k, g, p)) return rc;
-        // run_ops: GN_APPLY (xa, xb, stats, gamma, beta, out_act, out_raw; Ca, Cb, B, H, W, G, silu, resample; eps)
         GnApplyProblem& q = t[g];
         memset(&q, 0, sizeof(q));
-        q.xa = p[0]; q.xb = p[1]; q.stats = (const double*)p[2]; q.out_act = p[5]; q.out_raw = p[6]; q.H = (int)o.i[3]; q.W = (int)o.i[4];
-        ni += gn_apply_group_problem((int)o0.i[7], (int)(o0.i[0] + o0.i[1]), (int)o.i[2], c.dtype, geo.apply, g, q, it + ni);
+        q.xa = p[XA]; q.xb = p[XB]; q.stats = (const double*)p[STATS]; q.out_act = p[OUT_ACT]; q.out_raw = p[OUT_RAW]; q.H = (int)o.i[H]; q.W = (int)o.i[W];
+        ni += gn_apply_group_problem((int)o0.i[RESAMPLE], (int)(o0.i[CA] + o0.i[CB]), (int)o.i[B], c.dtype, geo.apply, g, q, it + ni);
     }
     STORM_CHECK(ni == geo.items, "storm_program_group: GroupNorm-apply items %lld != %lld", ni, geo.items);
-    go.apply.Ca = (int)o0.i[0]; go.apply.Cb = (int)o0.i[1]; go.apply.groups = (int)o0.i[5]; go.apply.resample = (int)o0.i[7]; go.apply.plan = geo.apply;
-    go.apply.gamma = static_cast<const float*>(p[3]); go.apply.beta = static_cast<const float*>(p[4]); go.apply.eps = o0.f[0];
+    go.apply.Ca = (int)o0.i[CA]; go.apply.Cb = (int)o0.i[CB]; go.apply.groups = (int)o0.i[G]; go.apply.resample = (int)o0.i[RESAMPLE]; go.apply.plan = geo.apply;
+    go.apply.gamma = static_cast<const float*>(p[GAMMA]); go.apply.beta = static_cast<const float*>(p[BETA]); go.apply.eps = o0.f[EPS];
     return 1;
 }
 int apply_launch(const GroupOp& go, const char* dev_table, const char* dev_tiles, int dtype, hipStream_t st) {
@@ -269,14 +273,15 @@ int apply_launch(const GroupOp& go, const char* dev_table, const char* dev_tiles
                                  go.apply.gamma, go.apply.beta, go.apply.eps, dtype, st);
 }
 
-// -- the three 16-bit convolution kinds.  STORM_OP_CONV: i[0] segments, i[1..3] B H W, i[4] outC, i[5] Cout, i[7] out_f32, i[8..] segment 0's Ca, Cb, CinP, rows, taps
+// -- the three 16-bit convolution kinds (STORM_OP_CONV)
+constexpr int CA0 = op_conv::iseg(0, op_conv::CA), CB0 = op_conv::iseg(0, op_conv::CB), TAPS0 = op_conv::iseg(0, op_conv::TAPS);   // segment 0's channels and taps
 bool conv_match(const storm_op& o, int dtype) {
     return is16(dtype) && switches().conv_variant < 0 &&     // a forced kernel family (tests, A/B) is honoured problem by problem
-           o.code == STORM_OP_CONV && (int)o.i[7] == 0;
+           o.code == STORM_OP_CONV && (int)o.i[op_conv::OUT_F32] == 0;
 }
 long long conv_tiles(const storm_op* const* ops, int k, int P, int th, int tw) {   // B x th-row x tw-pixel tiles of all problems
     long long t = 0;
-    for (int g = 0; g < P; ++g) t += (long long)ops[g][k].i[1] * cdiv(ops[g][k].i[2], th) * cdiv(ops[g][k].i[3], tw);
+    for (int g = 0; g < P; ++g) t += (long long)ops[g][k].i[op_conv::B] * cdiv(ops[g][k].i[op_conv::H], th) * cdiv(ops[g][k].i[op_conv::W], tw);
     return t;
 }
 // storm_conv_args of op k of every problem in c.args
@@ -295,8 +300,8 @@ int conv_group_args(GroupCtx& c, int k) {
 bool narrow_match(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo) {
     for (int g = 0; g < P; ++g) {
         const storm_op& o = ops[g][k];
-        if (!conv_match(o, dtype) || (int)o.i[4] != 8 || (int)o.i[0] != 1 || (int)o.i[8 + 4] != 9) return false;
-        if (o.i[5] != ops[0][k].i[5] || o.i[8] != ops[0][k].i[8] || o.i[9] != 0) return false;
+        if (!conv_match(o, dtype) || (int)o.i[op_conv::OUTC] != 8 || (int)o.i[op_conv::NSEG] != 1 || (int)o.i[TAPS0] != 9) return false;
+        if (o.i[op_conv::COUT] != ops[0][k].i[op_conv::COUT] || o.i[CA0] != ops[0][k].i[CA0] || o.i[CB0] != 0) return false;
     }
     geo.items = conv_tiles(ops, k, P, 20, 32);
     geo.table_bytes = conv_narrow_group_bytes(P); geo.tiles_bytes = align256(geo.items * (long long)sizeof(pipe::GroupTile));
@@ -317,8 +322,8 @@ int narrow_launch(const GroupOp& go, const char* dev_table, const char* dev_tile
 bool thin_match(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo) {
     for (int g = 0; g < P; ++g) {
         const storm_op& o = ops[g][k];
-        if (!conv_match(o, dtype) || (int)o.i[0] != 1 || (int)o.i[8] != 8 || (int)o.i[9] != 0 || (int)o.i[4] < 64) return false;
-        if (o.i[4] != ops[0][k].i[4] || o.i[8 + 4] != ops[0][k].i[8 + 4]) return false;
+        if (!conv_match(o, dtype) || (int)o.i[op_conv::NSEG] != 1 || (int)o.i[CA0] != 8 || (int)o.i[CB0] != 0 || (int)o.i[op_conv::OUTC] < 64) return false;
+        if (o.i[op_conv::OUTC] != ops[0][k].i[op_conv::OUTC] || o.i[TAPS0] != ops[0][k].i[TAPS0]) return false;
     }
     geo.items = 0; geo.table_bytes = conv_thin_group_bytes(P); geo.tiles_bytes = 0;
     return true;
@@ -338,8 +343,8 @@ int thin_launch(const GroupOp& go, const char* dev_table, const char*, int dtype
 bool pipe_match(const storm_op* const* ops, int k, int P, int dtype, GroupGeom& geo) {
     for (int g = 0; g < P; ++g) {
         const storm_op& o = ops[g][k];
-        if (!conv_match(o, dtype) || (int)o.i[4] <= 128 || (int)o.i[8 + 4] != 9) return false;
-        if (o.i[4] != ops[0][k].i[4] || o.i[5] != ops[0][k].i[5] || o.i[0] != ops[0][k].i[0]) return false;
+        if (!conv_match(o, dtype) || (int)o.i[op_conv::OUTC] <= 128 || (int)o.i[TAPS0] != 9) return false;
+        if (o.i[op_conv::OUTC] != ops[0][k].i[op_conv::OUTC] || o.i[op_conv::COUT] != ops[0][k].i[op_conv::COUT] || o.i[op_conv::NSEG] != ops[0][k].i[op_conv::NSEG]) return false;
     }
     geo.items = conv_tiles(ops, k, P, 8, 32);
     geo.table_bytes = align256((long long)P * sizeof(pipe::PipeParams)); geo.tiles_bytes = align256(geo.items * (long long)sizeof(pipe::GroupTile));
@@ -425,7 +430,7 @@ int storm::program_run_group(const storm_op* const* ops, int n_ops, void* const*
         for (int g = 0; g < P; ++g) {
             if (k == n_ops - 1 && (ops[g][k].code == STORM_OP_OUTPUT_HEAD || ops[g][k].code == STORM_OP_OUTPUT_PYRAMID)) {
                 storm_op head = ops[g][k];
-                head.i[4] = negate ? 1 : 0;
+                head.i[op_outpyr::NEGATE] = negate ? 1 : 0;         // (= op_head::NEGATE)
                 if (int rc = run_ops(&head, 1, bufs[g], n_bufs, dtype, s, nullptr)) return rc;
             } else if (int rc = run_ops(ops[g] + k, 1, bufs[g], n_bufs, dtype, s, nullptr)) return rc;
         }
@@ -461,9 +466,7 @@ extern "C" int storm_program_run_timed(const storm_op* ops, int n_ops, void* con
 // and which optional pointers are present, not on their values.
 extern "C" const char* storm_program_kernel_name(const storm_op* ops, int k, int dtype) {
     if (ops == nullptr || k < 0 || ops[k].code != STORM_OP_CONV) return "";
-    void* p[STORM_OP_NPTR];
-    for (int j = 0; j < STORM_OP_NPTR; ++j) p[j] = ops[k].p[j].buf >= 0 ? reinterpret_cast<void*>(uintptr_t(16)) : nullptr;
     storm_conv_args a;
-    conv_args_of(ops[k], p, dtype, a);
+    conv_shape_args_of(ops[k], dtype, a);
     return storm_conv_kernel_name(&a);
 }
