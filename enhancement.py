@@ -4,7 +4,8 @@
     python enhancement.py --test_dir noisy/ --enhanced_dir out/ --ckpt model.ckpt --mode storm \
         [--corrector ald --corrector-steps 1 --snr 0.5 --N 50]
 
-Additions: --precision {fp32,bf16}, --batch (equal-length utterances per sampler call), --seed / --utterance-seed, --resample /
+Additions: --precision {fp32,bf16}, --batch (equal-length utterances per sampler call), --seed / --utterance-seed, --sampler ode with
+--ode-method {RK45,RK23,DOP853} / --ode-rtol / --ode-atol (what the reference hands to scipy.integrate.solve_ivp), --resample /
 --output-sr (files of other rates than 16 kHz, resampled on the device) and multi-GPU sharding when launched with torchrun (one
 process per GPU, files dealt by length; no collectives in the sampler).  WAV I/O uses scipy.io.wavfile (torchaudio is not required)."""
 import glob
@@ -51,8 +52,11 @@ def main():
     p.add_argument("--corrector-steps", type=int, default=1)
     p.add_argument("--snr", type=float, default=0.5)
     p.add_argument("--N", type=int, default=50)
-    p.add_argument("--sampler", choices=("pc", "ode"), default="pc", help="(extension) ode: the probability-flow RK45 sampler of ScoreModel.enhance(sampler_type='ode') - "
+    p.add_argument("--sampler", choices=("pc", "ode"), default="pc", help="(extension) ode: the probability-flow sampler of ScoreModel.enhance(sampler_type='ode') - "
                    "BASELINE.json configs[4]; score-only mode, one step controller per file (the reference integrates one file per solve_ivp call)")
+    p.add_argument("--ode-method", choices=("RK45", "RK23", "DOP853"), default=None, help="with --sampler ode: solve_ivp's explicit method (default RK45)")
+    p.add_argument("--ode-rtol", type=float, default=None, help="with --sampler ode: relative tolerance of the step controller (default 1e-5)")
+    p.add_argument("--ode-atol", type=float, default=None, help="with --sampler ode: absolute tolerance of the step controller (default 1e-5)")
     p.add_argument("--precision", choices=("fp32", "bf16", "fp16"), default="fp32")
     p.add_argument("--batch", type=int, default=16)
     p.add_argument("--seed", type=int, default=None, help="Philox seed of the sampler noise (default: drawn from torch's RNG, as the reference)")
@@ -71,6 +75,9 @@ def main():
     args = p.parse_args()
     if args.seed is not None and args.utterance_seed is not None:
         raise SystemExit("--seed and --utterance-seed exclude each other")
+    ode_kw = {k: v for k, v in (("method", args.ode_method), ("rtol", args.ode_rtol), ("atol", args.ode_atol)) if v is not None}
+    if ode_kw and args.sampler != "ode":
+        raise SystemExit("--ode-method / --ode-rtol / --ode-atol: only with --sampler ode")
     if args.sampler == "ode" and args.mode != "score-only":
         raise SystemExit("--sampler ode: score-only mode (the reference's StoRM ODE path drops the conditioning, model.py:671-691)")
 
@@ -131,7 +138,7 @@ def main():
             outs = [x_hat[k, :lens[k]] for k in range(len(ids))]
         return ids, outs
 
-    skw = dict(sampler_type="ode", N=args.N) if args.sampler == "ode" else dict(corrector=args.corrector, N=args.N, corrector_steps=args.corrector_steps, snr=args.snr)
+    skw = dict(sampler_type="ode", N=args.N, **ode_kw) if args.sampler == "ode" else dict(corrector=args.corrector, N=args.N, corrector_steps=args.corrector_steps, snr=args.snr)
     keys = None if args.utterance_seed is None else [utterance_key(args.utterance_seed, f) for f in files]
     buckets = D.bucket_by_frames([lengths[i] for i in mine], args.batch)
     if args.mode in ("score-only", "storm") and args.group > 1 and len(buckets) > 1:

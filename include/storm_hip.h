@@ -422,6 +422,22 @@ int storm_rk_scaled_sumsq_rows(double* out, double* scratch, long long scratch_l
                                const float* const* K, const double* coef, int n_terms, const double* h_rows, double atol,
                                double rtol, int B, long long n_complex_row, storm_stream_t s);
 int storm_copy_rows(void* dst, const void* src, const int* row_mask, int B, long long row_bytes, storm_stream_t s);
+/* The wide forms: up to STORM_RK_MAX_TERMS stages, for solve_ivp's other explicit methods (sampling/__init__.py:71-141 passes
+ * `method` on to scipy: RK23's rows fit the forms above, DOP853 has 12 terms in a stage and 13 in its two error estimators,
+ * scipy/integrate/_ivp/rk.py DOP853._step_impl / _estimate_error_norm).  Types, h_rows and B as in the per-row forms above.
+ *   combine_rows_wide: storm_rk_combine_rows with n_terms in 1..13; for n_terms <= 7 the same bits.  16-byte stage accesses where
+ *                      the row length is even and K / out32 are 16-byte aligned.
+ *   error_pair_rows:   ONE pass over the stages for two coefficient rows: out[b] = row b's sum of |va|^2 / scale^2 and out[B + b]
+ *                      that of |vb|^2 / scale^2, v = h_rows[b] * sum_j coef[j] K[j][b], scale = atol + max(|xa|, |xb|) rtol
+ *                      (xb may be NULL); h_rows NULL = 1 (DOP853 applies |h| to the norm on the host).  The geometry of
+ *                      storm_rk_scaled_sumsq_rows (each sum is its bits for n_terms <= 7), no atomics; scratch: >= 2 *
+ *                      STORM_RK_ROW_BLOCKS * B doubles, out: 2 * B doubles. */
+enum { STORM_RK_MAX_TERMS = 13 };
+int storm_rk_combine_rows_wide(double* out64, float* out32, const double* x, const float* const* K, const double* coef, int n_terms,
+                               const double* h_rows, int B, long long n_complex_row, storm_stream_t s);
+int storm_rk_error_pair_rows(double* out, double* scratch, long long scratch_len, const double* xa, const double* xb,
+                             const float* const* K, const double* coef_a, const double* coef_b, int n_terms, const double* h_rows,
+                             double atol, double rtol, int B, long long n_complex_row, storm_stream_t s);
 /* fills z[B*n] complex with standard complex normal noise (Philox) */
 int storm_complex_randn(float* z, long long n_complex, uint64_t seed, uint64_t offset,
                         storm_stream_t s);

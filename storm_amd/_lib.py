@@ -134,6 +134,8 @@ _SIGNATURES = {
     "storm_rk_scaled_sumsq": ([_vp, _vp, _i, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_float), _i, _f, _f, _f, _ll, _vp], C.c_int),
     "storm_rk_combine_rows": ([_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _i, _ll, _vp], C.c_int),
     "storm_rk_scaled_sumsq_rows": ([_vp, _vp, _ll, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_double), _i, C.POINTER(C.c_double), C.c_double, C.c_double, _i, _ll, _vp], C.c_int),
+    "storm_rk_combine_rows_wide": ([_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _i, _ll, _vp], C.c_int),
+    "storm_rk_error_pair_rows": ([_vp, _vp, _ll, _vp, _vp, C.POINTER(_vp), C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_double), C.c_double, C.c_double, _i, _ll, _vp], C.c_int),
     "storm_copy_rows": ([_vp, _vp, C.POINTER(C.c_int), _i, _ll, _vp], C.c_int),
     "storm_complex_randn": ([_vp, _ll, _u64, _u64, _vp], C.c_int),
     "storm_complex_randn_rs": ([_vp, _i, _ll, _u64, _u64, _vp, _vp], C.c_int),

@@ -301,63 +301,101 @@ __global__ void sum_partials_kernel(const double* __restrict__ part, int n, doub
 // keeps the solver state in complex128 (it up-casts the complex64 state it is handed and only the right-hand side runs in
 // fp32, sampling/__init__.py:119-123): the state x is fp64 here too, the stages K are the fp32 network outputs, and the
 // algebra is fp64 - the accept / reject decisions then follow scipy's to rounding noise of 1e-16, not 1e-7.
-struct RkTermsD { const float* k[7]; double c[7]; int n; };
+// MAXT stages and NE coefficient rows over them (7 x 1: the storm_rk_*_rows entry points; STORM_RK_MAX_TERMS x 1 / x 2: the wide forms)
+template <int MAXT, int NE> struct RkTermsN { const float* k[MAXT]; double c[NE][MAXT]; int n; };
+using RkTermsD = RkTermsN<7, 1>;
 struct alignas(16) Cplx128 { double x, y; };
 struct RkRows { double h[STORM_RK_MAX_ROWS]; };
-// out64 = x + h_b * sum_j c_j K_j (complex128, may be NULL); out32 = the same rounded to complex64 (the next network input)
-__global__ void rk_combine_rows_kernel(double* __restrict__ out64, float* __restrict__ out32, const double* __restrict__ x, RkTermsD t,
-                                       RkRows hr, long long n2) {
+template <int V> using RkFloats = float __attribute__((ext_vector_type(2 * V)));   // V complex64: one 8- or 16-byte access
+// a[e][..] = sum_j c[e][j] K_j over the V complex elements from `at`, fp64, the terms in index order: the ONE body of every width,
+// so a sum over n terms is the same bits whichever entry point formed it.  Every stage is read once, for all NE rows.
+template <int MAXT, int NE, int V>
+__device__ __forceinline__ void rk_stage_sums(const RkTermsN<MAXT, NE>& t, long long at, double (&a)[NE][2 * V]) {
+#pragma unroll
+    for (int e = 0; e < NE; ++e)
+#pragma unroll
+        for (int q = 0; q < 2 * V; ++q) a[e][q] = 0.0;
+#pragma unroll
+    for (int j = 0; j < MAXT; ++j)
+        if (j < t.n) {
+            const RkFloats<V> k = *reinterpret_cast<const RkFloats<V>*>(t.k[j] + 2 * at);
+#pragma unroll
+            for (int e = 0; e < NE; ++e)
+#pragma unroll
+                for (int q = 0; q < 2 * V; ++q) a[e][q] = fma(t.c[e][j], (double)k[q], a[e][q]);
+        }
+}
+// out64 = x + h_b * sum_j c_j K_j (complex128, may be NULL); out32 = the same rounded to complex64 (the next network input).
+// A thread takes V complex elements at a time (V = 2: 16-byte stage reads; rows of an even length on 16-byte aligned pointers only).
+template <int MAXT, int V>
+__global__ void rk_combine_rows_kernel(double* __restrict__ out64, float* __restrict__ out32, const double* __restrict__ x,
+                                       RkTermsN<MAXT, 1> t, RkRows hr, long long n2) {
     const int b = blockIdx.y;
     const double h = hr.h[b];
-    const long long base = (long long)b * n2;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
-        double ax = 0.0, ay = 0.0;
+    const long long base = (long long)b * n2, nv = n2 / V;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) {
+        const long long at = base + i * V;
+        double a[1][2 * V];
+        rk_stage_sums<MAXT, 1, V>(t, at, a);
+        RkFloats<V> o32;
 #pragma unroll
-        for (int j = 0; j < 7; ++j)
-            if (j < t.n) {
-                const float2 k = reinterpret_cast<const float2*>(t.k[j])[base + i];
-                ax = fma(t.c[j], (double)k.x, ax); ay = fma(t.c[j], (double)k.y, ay);
-            }
-        const Cplx128 xx = reinterpret_cast<const Cplx128*>(x)[base + i];
-        const double ox = fma(h, ax, xx.x), oy = fma(h, ay, xx.y);
-        if (out64) reinterpret_cast<Cplx128*>(out64)[base + i] = Cplx128{ox, oy};
-        if (out32) reinterpret_cast<float2*>(out32)[base + i] = make_float2((float)ox, (float)oy);
+        for (int q = 0; q < V; ++q) {
+            const Cplx128 xx = reinterpret_cast<const Cplx128*>(x)[at + q];
+            const double ox = fma(h, a[0][2 * q], xx.x), oy = fma(h, a[0][2 * q + 1], xx.y);
+            if (out64) reinterpret_cast<Cplx128*>(out64)[at + q] = Cplx128{ox, oy};
+            o32[2 * q] = (float)ox; o32[2 * q + 1] = (float)oy;
+        }
+        if (out32) *reinterpret_cast<RkFloats<V>*>(out32 + 2 * at) = o32;
     }
 }
-// part[b][block] = that block's share of row b's scaled sum of squares: sum_c |v_c|^2 / (atol + max(|xa_c|, |xb_c|) rtol)^2 with
-// v = h_b * sum_j c_j K_j (t.n > 0), K[0] - K[1] (t.n == -2), K[0] (t.n == -1) or xa itself (t.n == -3).  The block count per row
-// depends on the row length only, so a row's sum is the same number whatever batch it sits in.
+// part[e][b][block] = that block's share of row b's scaled sum of squares: sum_c |v_c|^2 / (atol + max(|xa_c|, |xb_c|) rtol)^2 with
+// v = h_b * sum_j c[e][j] K_j (t.n > 0; NE = 2: both error estimators of DOP853 in one pass over the stages), K[0] - K[1]
+// (t.n == -2), K[0] (t.n == -1) or xa itself (t.n == -3; the three NE = 1 only).  The block count per row depends on the row
+// length only, so a row's sum is the same number whatever batch it sits in.
+template <int MAXT, int NE>
 __global__ void rk_scaled_sumsq_rows_kernel(double* __restrict__ part, const double* __restrict__ xa, const double* __restrict__ xb,
-                                            RkTermsD t, RkRows hr, double atol, double rtol, long long nc) {
-    __shared__ double red[4];
+                                            RkTermsN<MAXT, NE> t, RkRows hr, double atol, double rtol, long long nc) {
+    __shared__ double red[NE][4];
     const int b = blockIdx.y;
     const double h = hr.h[b];
     const long long base = (long long)b * nc;
-    double acc = 0.0;
+    double acc[NE];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) acc[e] = 0.0;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nc; i += (long long)gridDim.x * blockDim.x) {
         const Cplx128 a = reinterpret_cast<const Cplx128*>(xa)[base + i];
-        double vx = 0.0, vy = 0.0;
+        double v[NE][2];
         if (t.n > 0) {
+            rk_stage_sums<MAXT, NE, 1>(t, base + i, v);
 #pragma unroll
-            for (int j = 0; j < 7; ++j)
-                if (j < t.n) { const float2 k = reinterpret_cast<const float2*>(t.k[j])[base + i]; vx = fma(t.c[j], (double)k.x, vx); vy = fma(t.c[j], (double)k.y, vy); }
-            vx *= h; vy *= h;
-        } else if (t.n == -3) {
-            vx = a.x; vy = a.y;
+            for (int e = 0; e < NE; ++e) { v[e][0] *= h; v[e][1] *= h; }
         } else {
-            const float2 k = reinterpret_cast<const float2*>(t.k[0])[base + i];
-            vx = k.x; vy = k.y;
-            if (t.n == -2) { const float2 w = reinterpret_cast<const float2*>(t.k[1])[base + i]; vx -= (double)w.x; vy -= (double)w.y; }
+#pragma unroll
+            for (int e = 0; e < NE; ++e) v[e][0] = v[e][1] = 0.0;
+            if (t.n == -3) {
+                v[0][0] = a.x; v[0][1] = a.y;
+            } else {
+                const float2 k = reinterpret_cast<const float2*>(t.k[0])[base + i];
+                v[0][0] = k.x; v[0][1] = k.y;
+                if (t.n == -2) { const float2 w = reinterpret_cast<const float2*>(t.k[1])[base + i]; v[0][0] -= (double)w.x; v[0][1] -= (double)w.y; }
+            }
         }
         double m = sqrt(a.x * a.x + a.y * a.y);
         if (xb) { const Cplx128 q = reinterpret_cast<const Cplx128*>(xb)[base + i]; m = fmax(m, sqrt(q.x * q.x + q.y * q.y)); }
         const double sc = atol + m * rtol;
-        acc += (vx * vx + vy * vy) / (sc * sc);
+#pragma unroll
+        for (int e = 0; e < NE; ++e) acc[e] += (v[e][0] * v[e][0] + v[e][1] * v[e][1]) / (sc * sc);
     }
-    acc = wave_sum_d(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const double w = wave_sum_d(acc[e]);
+        if ((threadIdx.x & 63) == 0) red[e][threadIdx.x >> 6] = w;
+    }
     __syncthreads();
-    if (threadIdx.x == 0) part[(long long)b * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int e = 0; e < NE; ++e)
+            part[((long long)e * gridDim.y + b) * gridDim.x + blockIdx.x] = red[e][0] + red[e][1] + red[e][2] + red[e][3];
 }
 __global__ void sum_rows_kernel(const double* __restrict__ part, int n, int B, double* __restrict__ out) {   // one thread per row, fixed order
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -616,7 +654,7 @@ static int fill_terms_d(RkTermsD& t, const float* const* K, const double* coef, 
     const int np = n_terms > 0 ? n_terms : (n_terms == -3 ? 0 : -n_terms);
     STORM_CHECK(np == 0 || K, "storm_rk rows: null stage list");
     STORM_CHECK(n_terms < 0 || coef, "storm_rk rows: null coefficients");
-    for (int j = 0; j < 7; ++j) { t.k[j] = j < np ? K[j] : nullptr; t.c[j] = (n_terms > 0 && j < np) ? coef[j] : 0.0; }
+    for (int j = 0; j < 7; ++j) { t.k[j] = j < np ? K[j] : nullptr; t.c[0][j] = (n_terms > 0 && j < np) ? coef[j] : 0.0; }
     for (int j = 0; j < np; ++j) STORM_CHECK(K[j] != nullptr, "storm_rk rows: null stage %d", j);
     t.n = n_terms;
     return STORM_OK;
@@ -628,7 +666,7 @@ extern "C" int storm_rk_combine_rows(double* out64, float* out32, const double* 
     RkTermsD t; RkRows r;
     if (int rc = fill_terms_d(t, K, coef, n_terms)) return rc;
     if (int rc = fill_rows(r, h_rows, B)) return rc;
-    return launch_rows(rk_combine_rows_kernel, B, n_complex_row, s, out64, out32, x, t, r, n_complex_row);
+    return launch_rows(rk_combine_rows_kernel<7, 1>, B, n_complex_row, s, out64, out32, x, t, r, n_complex_row);
 }
 
 extern "C" int storm_rk_scaled_sumsq_rows(double* out, double* scratch, long long scratch_len, const double* xa, const double* xb,
@@ -641,8 +679,59 @@ extern "C" int storm_rk_scaled_sumsq_rows(double* out, double* scratch, long lon
     int nb = ew_blocks(n_complex_row);
     if (nb > STORM_RK_ROW_BLOCKS) nb = STORM_RK_ROW_BLOCKS;           // a function of the row length ONLY (see the kernel)
     STORM_CHECK(scratch_len >= (long long)nb * B, "storm_rk_scaled_sumsq_rows: scratch of %lld doubles < %lld", scratch_len, (long long)nb * B);
-    hipLaunchKernelGGL(rk_scaled_sumsq_rows_kernel, dim3(nb, B), dim3(256), 0, (hipStream_t)s, scratch, xa, xb, t, r, atol, rtol, n_complex_row);
+    hipLaunchKernelGGL((rk_scaled_sumsq_rows_kernel<7, 1>), dim3(nb, B), dim3(256), 0, (hipStream_t)s, scratch, xa, xb, t, r, atol, rtol, n_complex_row);
     hipLaunchKernelGGL(sum_rows_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)s, scratch, nb, B, out);
+    STORM_LAUNCH_CHECK();
+    return STORM_OK;
+}
+
+// ---- the wide forms: up to STORM_RK_MAX_TERMS stages (DOP853: 12 in a stage, 13 in its two error estimators) ----
+using RkTermsWide = RkTermsN<STORM_RK_MAX_TERMS, 1>;
+using RkTermsPair = RkTermsN<STORM_RK_MAX_TERMS, 2>;
+template <int NE>
+static int fill_terms_wide(RkTermsN<STORM_RK_MAX_TERMS, NE>& t, const float* const* K, const double* const (&coef)[NE], int n_terms) {
+    STORM_CHECK(n_terms >= 1 && n_terms <= STORM_RK_MAX_TERMS, "storm_rk wide: n_terms=%d outside 1..%d", n_terms, STORM_RK_MAX_TERMS);
+    STORM_CHECK(K, "storm_rk wide: null stage list");
+    for (int e = 0; e < NE; ++e) STORM_CHECK(coef[e], "storm_rk wide: null coefficients");
+    for (int j = 0; j < STORM_RK_MAX_TERMS; ++j) {
+        t.k[j] = j < n_terms ? K[j] : nullptr;
+        for (int e = 0; e < NE; ++e) t.c[e][j] = j < n_terms ? coef[e][j] : 0.0;
+    }
+    for (int j = 0; j < n_terms; ++j) STORM_CHECK(K[j] != nullptr, "storm_rk wide: null stage %d", j);
+    t.n = n_terms;
+    return STORM_OK;
+}
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+extern "C" int storm_rk_combine_rows_wide(double* out64, float* out32, const double* x, const float* const* K, const double* coef,
+                                          int n_terms, const double* h_rows, int B, long long n_complex_row, storm_stream_t s) {
+    STORM_CHECK((out64 || out32) && x && n_complex_row > 0 && h_rows, "storm_rk_combine_rows_wide: bad arguments");
+    RkTermsWide t; RkRows r;
+    const double* const cf[1] = {coef};
+    if (int rc = fill_terms_wide<1>(t, K, cf, n_terms)) return rc;
+    if (int rc = fill_rows(r, h_rows, B)) return rc;
+    // two complex elements per thread where every row starts on a 16-byte boundary (complex128 always does)
+    bool pair = n_complex_row % 2 == 0 && (!out32 || aligned16(out32));
+    for (int j = 0; j < n_terms; ++j) pair = pair && aligned16(K[j]);
+    if (pair)
+        return launch_rows(rk_combine_rows_kernel<STORM_RK_MAX_TERMS, 2>, B, n_complex_row / 2, s, out64, out32, x, t, r, n_complex_row);
+    return launch_rows(rk_combine_rows_kernel<STORM_RK_MAX_TERMS, 1>, B, n_complex_row, s, out64, out32, x, t, r, n_complex_row);
+}
+
+extern "C" int storm_rk_error_pair_rows(double* out, double* scratch, long long scratch_len, const double* xa, const double* xb,
+                                        const float* const* K, const double* coef_a, const double* coef_b, int n_terms,
+                                        const double* h_rows, double atol, double rtol, int B, long long n_complex_row, storm_stream_t s) {
+    STORM_CHECK(out && scratch && xa && n_complex_row > 0, "storm_rk_error_pair_rows: bad arguments");
+    RkTermsPair t; RkRows r;
+    const double* const cf[2] = {coef_a, coef_b};
+    if (int rc = fill_terms_wide<2>(t, K, cf, n_terms)) return rc;
+    if (int rc = fill_rows(r, h_rows, B)) return rc;
+    int nb = ew_blocks(n_complex_row);
+    if (nb > STORM_RK_ROW_BLOCKS) nb = STORM_RK_ROW_BLOCKS;           // the geometry of storm_rk_scaled_sumsq_rows: the row length ONLY
+    STORM_CHECK(scratch_len >= 2LL * nb * B, "storm_rk_error_pair_rows: scratch of %lld doubles < %lld", scratch_len, 2LL * nb * B);
+    hipLaunchKernelGGL((rk_scaled_sumsq_rows_kernel<STORM_RK_MAX_TERMS, 2>), dim3(nb, B), dim3(256), 0, (hipStream_t)s, scratch, xa, xb, t, r,
+                       atol, rtol, n_complex_row);
+    hipLaunchKernelGGL(sum_rows_kernel, dim3((2 * B + 63) / 64), dim3(64), 0, (hipStream_t)s, scratch, nb, 2 * B, out);   // out[e * B + b]
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }

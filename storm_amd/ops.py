@@ -570,7 +570,7 @@ def _kptrs(K):
     return arr
 
 
-RK_MAX_ROWS, RK_ROW_BLOCKS = 128, 256          # include/storm_hip.h: STORM_RK_MAX_ROWS, STORM_RK_ROW_BLOCKS
+RK_MAX_ROWS, RK_ROW_BLOCKS, RK_MAX_TERMS = 128, 256, 13          # include/storm_hip.h: STORM_RK_MAX_ROWS, STORM_RK_ROW_BLOCKS, STORM_RK_MAX_TERMS
 
 
 def _hrows(h, B):
@@ -581,21 +581,52 @@ def _hrows(h, B):
     return (C.c_double * B)(*[float(v) for v in h])
 
 
-def rk_combine_rows(x64, K, coef, h_rows, want64=False):
+def rk_combine_rows(x64, K, coef, h_rows, want64=False, entry="storm_rk_combine_rows"):
     """x64[b] + h_rows[b] * sum_j coef[j] K[j][b]: one Runge-Kutta stage of B utterances with their own step sizes.  x64 is
     the complex128 solver state, K complex64 stages; returns the complex64 rounding (the next network input), with
     want64=True (out64, out32)."""
     B = x64.shape[0]
     if B > RK_MAX_ROWS:                      # the kernels take their step sizes as a 128-entry argument array: larger batches in row blocks
-        parts = [rk_combine_rows(x64[i:i + RK_MAX_ROWS], [k[i:i + RK_MAX_ROWS] for k in K], coef, h_rows[i:i + RK_MAX_ROWS], want64)
+        parts = [rk_combine_rows(x64[i:i + RK_MAX_ROWS], [k[i:i + RK_MAX_ROWS] for k in K], coef, h_rows[i:i + RK_MAX_ROWS], want64, entry)
                  for i in range(0, B, RK_MAX_ROWS)]
         return (torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])) if want64 else torch.cat(parts)
     out32 = torch.empty(x64.shape, dtype=torch.complex64, device=x64.device)
     out64 = torch.empty_like(x64) if want64 else None
     cf = (C.c_double * len(K))(*[float(c) for c in coef])
-    L.check(L.lib().storm_rk_combine_rows(L.ptr(_r(out64)) if want64 else None, L.ptr(_r(out32)), L.ptr(_r(x64)), _kptrs(K), cf, len(K),
-                                          _hrows(h_rows, B), B, _n_per_batch(x64), L.stream()), "storm_rk_combine_rows")
+    L.check(getattr(L.lib(), entry)(L.ptr(_r(out64)) if want64 else None, L.ptr(_r(out32)), L.ptr(_r(x64)), _kptrs(K), cf, len(K),
+                                    _hrows(h_rows, B), B, _n_per_batch(x64), L.stream()), entry)
     return (out64, out32) if want64 else out32
+
+
+def rk_combine_rows_wide(x64, K, coef, h_rows, want64=False):
+    """rk_combine_rows for up to RK_MAX_TERMS stages (DOP853's rows have 12): the same bits for up to 7"""
+    return rk_combine_rows(x64, K, coef, h_rows, want64, entry="storm_rk_combine_rows_wide")
+
+
+def _rk_scratch_for(device, need):
+    key = (str(device), threading.get_ident())          # (per host thread: grouped micro-batches interleave their launches on one stream)
+    if key not in _rk_scratch or _rk_scratch[key].numel() < need:
+        _rk_scratch[key] = torch.empty(need, dtype=torch.float64, device=device)
+    return _rk_scratch[key]
+
+
+def rk_error_pair_rows(xa, xb, K, coef_a, coef_b, h_rows, atol, rtol):
+    """Device float64 [2, B] from ONE pass over up to RK_MAX_TERMS stages: [0, b] / [1, b] = row b's sum of |v|^2 / (atol + max(|xa|,
+    |xb|) rtol)^2 with v = h_b sum coef_a[j] K[j] / h_b sum coef_b[j] K[j] (h_rows None: 1) - DOP853's two error estimators.  Each
+    sum is what rk_scaled_sumsq_rows gives for that coefficient row; a row's values do not depend on the other rows of the batch."""
+    B = xa.shape[0]
+    if B > RK_MAX_ROWS:
+        return torch.cat([rk_error_pair_rows(xa[i:i + RK_MAX_ROWS], xb[i:i + RK_MAX_ROWS] if xb is not None else None,
+                                             [k[i:i + RK_MAX_ROWS] for k in K], coef_a, coef_b,
+                                             h_rows[i:i + RK_MAX_ROWS] if h_rows is not None else None, atol, rtol)
+                          for i in range(0, B, RK_MAX_ROWS)], dim=1)
+    scratch = _rk_scratch_for(xa.device, 2 * RK_ROW_BLOCKS * B)
+    out = torch.empty(2, B, dtype=torch.float64, device=xa.device)
+    ca, cb = [(C.c_double * len(K))(*[float(c) for c in cf]) for cf in (coef_a, coef_b)]
+    L.check(L.lib().storm_rk_error_pair_rows(L.ptr(out), L.ptr(scratch), scratch.numel(), L.ptr(_r(xa)), L.ptr(_r(xb)) if xb is not None else None,
+                                             _kptrs(K) if K else None, ca, cb, len(K), _hrows(h_rows, B), float(atol), float(rtol), B,
+                                             _n_per_batch(xa), L.stream()), "storm_rk_error_pair_rows")
+    return out
 
 
 def rk_scaled_sumsq_rows(xa, xb, K, coef, h_rows, atol, rtol, mode=None):
@@ -608,14 +639,11 @@ def rk_scaled_sumsq_rows(xa, xb, K, coef, h_rows, atol, rtol, mode=None):
                                                [k[i:i + RK_MAX_ROWS] for k in K], coef,
                                                h_rows[i:i + RK_MAX_ROWS] if h_rows is not None else None, atol, rtol, mode)
                           for i in range(0, B, RK_MAX_ROWS)])
-    key = (str(xa.device), threading.get_ident())       # (per host thread: grouped micro-batches interleave their launches on one stream)
-    need = RK_ROW_BLOCKS * B
-    if key not in _rk_scratch or _rk_scratch[key].numel() < need:
-        _rk_scratch[key] = torch.empty(need, dtype=torch.float64, device=xa.device)
+    scratch = _rk_scratch_for(xa.device, RK_ROW_BLOCKS * B)
     out = torch.empty(B, dtype=torch.float64, device=xa.device)
     n_terms = len(K) if mode is None else mode
     cf = (C.c_double * max(1, len(K)))(*[float(c) for c in (coef if coef is not None else [0.0] * max(1, len(K)))])
-    L.check(L.lib().storm_rk_scaled_sumsq_rows(L.ptr(out), L.ptr(_rk_scratch[key]), _rk_scratch[key].numel(), L.ptr(_r(xa)),
+    L.check(L.lib().storm_rk_scaled_sumsq_rows(L.ptr(out), L.ptr(scratch), scratch.numel(), L.ptr(_r(xa)),
                                                L.ptr(_r(xb)) if xb is not None else None, _kptrs(K) if K else None, cf, n_terms,
                                                _hrows(h_rows, B), float(atol), float(rtol), B, _n_per_batch(xa), L.stream()),
             "storm_rk_scaled_sumsq_rows")
