@@ -6,7 +6,8 @@
 
 Additions: --precision {fp32,bf16}, --batch (equal-length utterances per sampler call), --seed / --utterance-seed, --sampler ode with
 --ode-method {RK45,RK23,DOP853} / --ode-rtol / --ode-atol (what the reference hands to scipy.integrate.solve_ivp), --resample /
---output-sr (files of other rates than 16 kHz, resampled on the device) and multi-GPU sharding when launched with torchrun (one
+--output-sr (files of other rates than 16 kHz, resampled on the device), --window / --overlap / --ramp / --skip-silent (long recordings as
+overlapping windows, pooled into full batches and cross-faded on the device: enhance_long) and multi-GPU sharding when launched with torchrun (one
 process per GPU, files dealt by length; no collectives in the sampler).  WAV I/O uses scipy.io.wavfile (torchaudio is not required)."""
 import glob
 import hashlib
@@ -71,7 +72,13 @@ def main():
                    "(SpecsDataModule.resample, scipy.signal.resample_poly's filter), batching and seeding work on the 16 kHz signals, and every enhanced file is "
                    "resampled back and written at its own rate with its own sample count.  Without it a file of another rate is refused, as upstream")
     p.add_argument("--output-sr", choices=("input", "model"), default="input", help="with --resample: write every file at its own rate (input) or at 16 kHz (model)")
-    p.add_argument("--dist-world1", action="store_true", help="with ONE rank: form the RCCL process group anyway (dry run of the sharded path on one GPU)")
+    p.add_argument("--window", type=float, default=None, help="(extension) seconds: a file longer than this is enhanced as overlapping windows of this length, the windows of "
+                   "all files pooled into batches of --batch rows of one shape and cross-faded back on the device (enhance_long; 4.088 s = 512 frames is the "
+                   "benchmark's shape).  Absent: every file is one row, as upstream")
+    p.add_argument("--overlap", type=float, default=0.512, help="with --window: seconds two neighbouring windows share (at most half a window)")
+    p.add_argument("--ramp", choices=("hann", "linear"), default="hann", help="with --window: the cross-fade's weights over the overlap")
+    p.add_argument("--skip-silent", action="store_true", help="with --window: windows whose every sample is zero are not sampled and come out as zeros")
+    p.add_argument("--dist-world1",action="store_true", help="with ONE rank: form the RCCL process group anyway (dry run of the sharded path on one GPU)")
     args = p.parse_args()
     if args.seed is not None and args.utterance_seed is not None:
         raise SystemExit("--seed and --utterance-seed exclude each other")
@@ -140,6 +147,17 @@ def main():
 
     skw = dict(sampler_type="ode", N=args.N, **ode_kw) if args.sampler == "ode" else dict(corrector=args.corrector, N=args.N, corrector_steps=args.corrector_steps, snr=args.snr)
     keys = None if args.utterance_seed is None else [utterance_key(args.utterance_seed, f) for f in files]
+    if args.window is not None:
+        # long recordings: this rank's files in ONE enhance_long call - the windows of all files longer than --window pooled into full batches
+        # of one shape, cross-faded on the device; shorter files as below.  A file's key: its utterance key, --seed + its index, or drawn.
+        file_keys = [keys[i] for i in mine] if keys is not None else (None if args.seed is None else [args.seed + i for i in mine])
+        outs = model.enhance_long([wavs[i][0] for i in mine], window=round(args.window * model_sr), overlap=round(args.overlap * model_sr),
+                                  batch=args.batch, ramp=args.ramp, keys=file_keys, skip_silent=args.skip_silent,
+                                  grouped=args.group if args.mode != "denoiser-only" and args.group > 1 else False, **skw) if mine else []
+        for i, x in zip(mine, outs):
+            write_enhanced(i, x)
+        D.finish()
+        return
     buckets = D.bucket_by_frames([lengths[i] for i in mine], args.batch)
     if args.mode in ("score-only", "storm") and args.group > 1 and len(buckets) > 1:
         # a ragged set of files: micro-batches of 2 - 3 rows each - their score evaluations share launches (storm_ncsnpp_forward_group)

@@ -528,6 +528,29 @@ int storm_lsd_rows(const float* spec_hat, const float* spec, double* out, void* 
                    const int* row_frames, double eps, storm_stream_t st);
 
 /* ------------------------------------------------------------------------------------------
+ * Long recordings: a recording longer than one window of W samples is enhanced as n overlapping windows (overlap V, 1 <= V <= W / 2, hop
+ * H = W - V, window k starts at k H, n = ceil((L - V) / H)) and stitched back.  Output sample m < L of a recording:
+ *   k = min(m / H, n - 1), j = m - k H, cur = window_k[j];
+ *   k > 0 and j < V:  prev = window_{k-1}[j + H],  out = prev + ramp[j] * (cur - prev)   (three fp32 operations in this order, not contracted)
+ *   otherwise:        out = cur.
+ * A skipped window reads as zeros; samples from L up to `width` are zero.  Windows cut from a signal therefore stitch back to it bit for bit.
+ *
+ * storm_crossfade_ramp (host, no device): ramp[j], j = 0 .. V - 1, designed in fp64 and rounded to fp32 once into the CALLER's host memory
+ *   of V floats; STORM_RAMP_HANN: sin(pi / 2 (j + 1) / (V + 1))^2, STORM_RAMP_LINEAR: (j + 1) / (V + 1).
+ * storm_crossfade_rows: ONE launch stitches R recordings.  pool: the enhanced windows, fp32 [N][W] with row stride pool_stride; out fp32
+ *   [R][width] with row stride out_stride; device int32 arrays: rec_len[R] (samples), rec_windows[R] (n_r, with (n_r - 1) H + V < rec_len[r]
+ *   <= (n_r - 1) H + W, or n_r = 1 and rec_len[r] <= W), rec_first[R] (index of the recording's first entry in win_row) and
+ *   win_row[sum n_r]: the pool row of every window in recording order, -1 for a skipped window; ramp: that table on the device.
+ *   One workgroup computes STORM_CROSSFADE_TILE outputs of one recording; no atomics - an output's bits depend on its own recording's
+ *   windows only. */
+#define STORM_CROSSFADE_TILE 1024
+enum { STORM_RAMP_HANN = 0, STORM_RAMP_LINEAR = 1 };
+int storm_crossfade_ramp(int V, int kind, float* ramp);
+int storm_crossfade_rows(const float* pool, int N, long long pool_stride, float* out, int R, long long width, long long out_stride,
+                         const int* rec_len, const int* rec_windows, const int* rec_first, const int* win_row, int W, int V,
+                         const float* ramp, storm_stream_t st);
+
+/* ------------------------------------------------------------------------------------------
  * ConvTasNet (backbones/convtasnet.py): the time-domain denoiser.  Activations are channels-last [B][L][C] in `dtype`
  * (C % 8 == 0); the TCN's running sums `output` / `skip_connection` are fp32 [B][L][BN]; statistics are fp32.  A global layer
  * norm (GroupNorm(1, C, eps) over all of C x L of a row) is never materialised: the producing kernel writes per-wave

@@ -22,6 +22,8 @@ OP_NPTR, OP_NINT, OP_NFLT = 13, 24, 4
 ABI_VERSION = 2                  # include/storm_hip.h: STORM_ABI_VERSION
 METRICS_CHUNK = 16384            # include/storm_hip.h: STORM_METRICS_CHUNK, the samples one workgroup of storm_energy_ratios_rows sums
 RESAMPLE_TILE = 1024             # include/storm_hip.h: STORM_RESAMPLE_TILE, the outputs one workgroup of storm_resample_poly computes
+CROSSFADE_TILE = 1024            # include/storm_hip.h: STORM_CROSSFADE_TILE, the outputs one workgroup of storm_crossfade_rows computes
+RAMP_KINDS = {"hann": 0, "linear": 1}        # include/storm_hip.h: STORM_RAMP_HANN, STORM_RAMP_LINEAR
 
 
 class StormError(RuntimeError):
@@ -150,7 +152,9 @@ _SIGNATURES = {
     "storm_energy_ratios_rows": ([_vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _ll, _vp, _vp], C.c_int),
     "storm_lsd_scratch_bytes": ([_i, _i, _i], C.c_longlong),
     "storm_lsd_rows": ([_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, C.c_double, _vp], C.c_int),
-    "storm_tasnet_num_partials": ([_i, _i, _i], C.c_int),
+    "storm_crossfade_ramp": ([_i, _i, _vp], C.c_int),
+    "storm_crossfade_rows": ([_vp, _i, _ll, _vp, _i, _ll, _ll, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp], C.c_int),
+    "storm_tasnet_num_partials":([_i, _i, _i], C.c_int),
     "storm_tasnet_frames": ([_ll, _i], C.c_int),
     "storm_tasnet_encode": ([_vp, _ll, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp], C.c_int),
     "storm_tasnet_gln_finalize": ([_vp, _vp, _i, _i, _ll, _f, _vp], C.c_int),

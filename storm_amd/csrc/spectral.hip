@@ -341,3 +341,6 @@ extern "C" int storm_resample_poly(const float* x, float* y, const float* taps, 
 
 // ---- evaluation metrics of enhanced audio (storm_energy_ratios_rows, storm_lsd_rows): kernels and entry points ----
 #include "metrics.h"
+
+// ---- long recordings (storm_crossfade_rows, storm_crossfade_ramp): the stitch of enhanced windows, kernel and entry points ----
+#include "longform.h"

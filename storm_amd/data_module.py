@@ -80,14 +80,21 @@ class SpecsDataModule:
         """frames of one utterance after pad_spec (util/other.py:102-109): utterances with equal values can share a batch"""
         return ops.round_up(1 + int(length) // self.hop_length, pad_to)
 
-    def wav_to_spec(self, wav, pad_to=64, lengths=None):
-        """wav [B, L] -> (Y [B,1,F,Tpad] = pad_spec(spec_fwd(stft(wav / peak))), peak [B])  in two launches.
-        lengths: per-row sample counts of a ragged batch (rows zero filled past them, one padded frame count for all)."""
+    def wav_to_spec(self, wav, pad_to=64, lengths=None, peak=None):
+        """wav [B, L] (rows may be a strided view) -> (Y [B,1,F,Tpad] = pad_spec(spec_fwd(stft(wav / peak))), peak [B])  in two launches.
+        lengths: per-row sample counts of a ragged batch (rows zero filled past them, one padded frame count for all).
+        peak: fp32 [B], the rows' normalisation factors from outside (the windows of a long recording carry the RECORDING's peak);
+        None: every row's own peak."""
         if lengths is not None:
             tp = {self.padded_frames(v, pad_to) for v in lengths}
             if len(tp) != 1 or max(int(v) for v in lengths) != wav.shape[1]:
                 raise ValueError(f"a ragged batch must share one padded frame count and be as wide as its longest row: {sorted(tp)}")
-        peak = ops.peak_abs(wav, lengths)
+        if peak is None:
+            peak = ops.peak_abs(wav, lengths)
+        else:
+            peak = peak.to(device=wav.device, dtype=torch.float32).reshape(-1).contiguous()
+            if peak.shape[0] != wav.shape[0]:
+                raise ValueError(f"peak has {peak.shape[0]} entries for a batch of {wav.shape[0]} rows")
         Y = ops.stft(wav, peak, n_fft=self.n_fft, hop=self.hop_length, spec_factor=self.spec_factor,
                      spec_abs_exponent=self.spec_abs_exponent, pad_to=pad_to, window=self.window_type, lengths=lengths)
         return Y.unsqueeze(1), peak

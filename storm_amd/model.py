@@ -6,7 +6,9 @@ DiscriminativeModel :320, StochasticRegenerationModel :392) without Lightning: `
 ``validation_step`` logs it (valid_loss), forward only.  Training methods are out of scope.
 
 New surface (not in the reference): ``enhance_batch`` (several utterances per call, equal to
-per-utterance ``enhance`` calls), ``set_precision`` and the ``noise_fn`` / ``seed`` / ``row_seeds`` sampler knobs.
+per-utterance ``enhance`` calls; also on ``DiscriminativeModel``), ``enhance_long`` (recordings of any lengths as overlapping windows,
+pooled into batches of one shape and cross-faded on the device), ``set_precision`` and the ``noise_fn`` / ``seed`` / ``row_seeds`` /
+``peak`` knobs.
 """
 import time
 import warnings
@@ -162,13 +164,17 @@ class _Base(nn.Module):
     def _istft(self, spec, length=None):
         return self.data_module.istft(spec, length)
 
-    def _prepare(self, y, lengths=None):
+    def _prepare(self, y, lengths=None, peak=None):
         """model.py:282-286 for a batch: y [B, L] host/device -> (Y [B,1,F,Tpad], peak [B], L).  lengths: the rows' own sample
-        counts when utterances of different lengths share the batch (same padded frame count; rows zero filled)."""
+        counts when utterances of different lengths share the batch (same padded frame count; rows zero filled).  peak: fp32 [B],
+        the rows' normalisation factors from outside instead of their own peaks (the windows of a long recording: enhance_long).
+        Rows that are contiguous are read where they lie (the overlapping windows of a recording are a strided view, not a copy)."""
         if y.dim() != 2:
             raise ValueError("expected a waveform batch [B, L]")
-        yd = y.to(device=self.device, dtype=torch.float32).contiguous()
-        Y, peak = self.data_module.wav_to_spec(yd, pad_to=64, lengths=lengths)
+        yd = y.to(device=self.device, dtype=torch.float32)
+        if yd.stride(1) != 1:
+            yd = yd.contiguous()
+        Y, peak = self.data_module.wav_to_spec(yd, pad_to=64, lengths=lengths, peak=peak)
         return Y, peak, y.size(1)
 
     # ---- audio at another rate than the model's (an extension: upstream asserts 16 kHz input, enhancement.py:69) -----------
@@ -230,7 +236,7 @@ class _Base(nn.Module):
         return getattr(self, "score_net", None) or self.dnn
 
     def enhance_stream(self, batches, grouped=True, return_nfe=False, seed=None, seeds=None, noise_fns=None, width=None, row_seeds=None,
-                       **kwargs):
+                       peaks=None, **kwargs):
         """(ScoreModel and StochasticRegenerationModel.)  A stream of ragged micro-batches (BASELINE.json configs[4]) in lockstep: `batches` = [(y [b, L], lengths or None), ...] as
         storm_amd.distributed.bucket_by_frames forms them.  Every micro-batch runs enhance_batch - the same sampler, noise stream and
         (ODE) per-row step control as its own call - but the score evaluations of all micro-batches that are still running share ONE
@@ -240,6 +246,7 @@ class _Base(nn.Module):
         row_seeds: one list of per-row Philox keys per micro-batch (enhance_batch's row_seeds) instead of seed / seeds / noise_fns: every
         utterance draws what its own batch-1 run with that key draws, whatever micro-batch it is in.
         width: at most this many micro-batches in flight (None = all); a finished one is replaced by the next of the list (storm_amd.sampling.grouped.run_grouped).
+        peaks: one entry per micro-batch, enhance_batch's peak (fp32 [b]) or None for the rows' own peaks.
         Returns the list of enhanced batches (and the mean evaluations per utterance with return_nfe); self.last_nfev_stream = the
         evaluations every micro-batch executed."""
         from .sampling.grouped import run_grouped
@@ -248,6 +255,8 @@ class _Base(nn.Module):
                 raise ValueError("row_seeds cannot be combined with seed, seeds or noise_fns")
             if len(row_seeds) != len(batches):
                 raise ValueError(f"row_seeds has {len(row_seeds)} key lists for {len(batches)} micro-batches")
+        if peaks is not None and len(peaks) != len(batches):
+            raise ValueError(f"peaks has {len(peaks)} entries for {len(batches)} micro-batches")
         outs = [None] * len(batches)
 
         def one(k):
@@ -261,6 +270,8 @@ class _Base(nn.Module):
                 kw["noise_fn"] = noise_fns[k]                  # (parity runs: the draws of micro-batch k)
             if row_seeds is not None:
                 kw["row_seeds"] = row_seeds[k]
+            if peaks is not None and peaks[k] is not None:
+                kw["peak"] = peaks[k]
             return self.enhance_batch(yb, lengths=bl, return_nfe=True, **kw)
         fns = [(lambda k=k: one(k)) for k in range(len(batches))]
         res, batcher = run_grouped(self._score_network(), fns, device=self.device, width=width) if grouped else ([f() for f in fns], None)
@@ -271,6 +282,128 @@ class _Base(nn.Module):
             rows = sum(b[0].shape[0] for b in batches)
             return outs, sum(r[1] * b[0].shape[0] for r, b in zip(res, batches)) / rows
         return outs
+
+    _has_sampler = True                  # (DiscriminativeModel: False - one forward pass, no noise keys)
+
+    def enhance_long(self, recordings, window=65408, overlap=8192, batch=16, ramp="hann", keys=None, seed=None, sr=None,
+                     skip_silent=False, grouped=False, return_nfe=False, **sampler_kwargs):
+        """Recordings of any lengths (a list of 1-D or [1, L] waveforms, host or device) -> the list of enhanced 1-D waveforms on the
+        device, each with its input's sample count.  window / overlap (W, V; 16 kHz samples, 1 <= V <= W // 2, hop H = W - V): a
+        recording of more than W samples at 16 kHz becomes n = ceil((L - V) / H) windows starting at k H - the [n, W] view of stride H of
+        the recording zero filled to (n - 1) H + W (ops.window_plan).  The windows of ALL such recordings form one pool in (recording,
+        window) order; every run of `batch` of them is ONE enhance_batch call of the shape [b, W] with peak = the RECORDING's peak per row
+        (the reference normalises the whole input, model.py:282-286, and a training crop by its file's factor, data_module.py:92-114)
+        and row_seeds = ops.window_key(recording key, k), so a window's result does not depend on what it is batched with; after the last
+        batch ONE ops.crossfade_rows launch cross-fades the windows of all recordings (ramp: 'hann' or 'linear', ops.crossfade_ramp).
+        A recording of at most W samples runs as it always did: storm_amd.distributed.bucket_by_frames + enhance_batch(lengths=...,
+        row_seeds=[its key]).
+        keys: one Philox key per recording; seed=s: recording i has the key s + i; neither: drawn from torch's generator
+        (DiscriminativeModel ignores all three).  sr: the recordings' sample rate, one for all or one each - a recording is resampled to
+        16 kHz as a whole, windowed there, stitched, resampled back and trimmed to its input sample count.
+        skip_silent: windows whose every sample is zero are not sampled and read as zeros in the stitch.
+        grouped (ScoreModel, StochasticRegenerationModel): the batches run in lockstep through enhance_stream - True: 8 in flight, an
+        int: that many - instead of one after the other.  return_nfe: also the score evaluations of every sampled row, summed.
+        sampler_kwargs: enhance_batch's (sampler_type, N, corrector, snr, ...)."""
+        from . import ops
+        from .distributed import bucket_by_frames
+        dm = self.data_module
+        W, V = int(window), int(overlap)
+        if V < 1 or V > W // 2:
+            raise ValueError(f"overlap={V} lies outside [1, window // 2] for window={W}")
+        if W <= dm.n_fft // 2:
+            raise ValueError(f"window={W} is too short for the STFT's reflect padding by n_fft // 2 = {dm.n_fft // 2} samples")
+        if int(batch) < 1:
+            raise ValueError(f"batch={batch}")
+        for name in ("row_seeds", "lengths", "peak", "noise_fn"):
+            if name in sampler_kwargs:
+                raise ValueError(f"enhance_long forms {name} itself")
+        if keys is not None and seed is not None:
+            raise ValueError("keys and seed exclude each other")
+        R = len(recordings)
+        if keys is not None:
+            keys = [int(v) for v in keys]
+            if len(keys) != R:
+                raise ValueError(f"keys has {len(keys)} entries for {R} recordings")
+        elif seed is not None:
+            keys = [int(seed) + i for i in range(R)]
+        elif self._has_sampler:
+            keys = [int(v) for v in torch.randint(2 ** 62, (R,))]
+        else:
+            keys = [0] * R
+        rates = list(sr) if isinstance(sr, (list, tuple)) else [sr] * R
+        if len(rates) != R:
+            raise ValueError(f"sr has {len(rates)} entries for {R} recordings")
+        H = W - V
+        with torch.no_grad():
+            x16, counts = [], []
+            for i, w in enumerate(recordings):
+                if w.dim() == 2 and w.shape[0] == 1:
+                    w = w[0]
+                if w.dim() != 1 or w.numel() < 1:
+                    raise ValueError(f"recordings[{i}]: expected a waveform [L] or [1, L], got {tuple(w.shape)}")
+                w = w.to(device=self.device, dtype=torch.float32)
+                counts.append(w.numel())
+                x16.append(dm.resample(w, int(rates[i]), dm.sample_rate) if self._off_rate(rates[i]) else w)
+            long_ids = [i for i in range(R) if x16[i].numel() > W]
+            short_ids = [i for i in range(R) if x16[i].numel() <= W]
+            # ---- the pool: every window of every long recording, in (recording, window) order
+            win_row, rec_windows, entries = [], [], []                # entries: (view [n, W], k, peak [1], key) of the windows that are sampled
+            for i in long_ids:
+                n, padded = ops.window_plan(x16[i].numel(), W, V)
+                buf = torch.zeros(padded, dtype=torch.float32, device=self.device)
+                buf[:x16[i].numel()] = x16[i]
+                view = buf.as_strided((n, W), (H, 1))
+                pk = ops.peak_abs(x16[i].reshape(1, -1))
+                silent = (ops.peak_abs(view) <= ops.PEAK_FLOOR).tolist() if skip_silent else [False] * n
+                rec_windows.append(n)
+                for k in range(n):
+                    win_row.append(-1 if silent[k] else len(entries))
+                    if not silent[k]:
+                        entries.append((view, k, pk, ops.window_key(keys[i], k)))
+            jobs = []                                                 # (y [b, .], lengths, peak, row_seeds, where its rows go)
+            for j0 in range(0, len(entries), int(batch)):
+                run = entries[j0:j0 + int(batch)]
+                one_view = all(e[0] is run[0][0] for e in run) and [e[1] for e in run] == list(range(run[0][1], run[0][1] + len(run)))
+                rows = run[0][0][run[0][1]:run[0][1] + len(run)] if one_view else torch.stack([e[0][e[1]] for e in run])
+                jobs.append((rows, None, torch.cat([e[2] for e in run]), [e[3] for e in run], ("pool", j0)))
+            lens = [x16[i].numel() for i in short_ids]
+            for bucket in bucket_by_frames(lens, int(batch), hop=dm.hop_length):
+                bl = [lens[k] for k in bucket]
+                y = torch.zeros(len(bucket), max(bl), dtype=torch.float32, device=self.device)
+                for row, k in enumerate(bucket):
+                    y[row, :bl[row]] = x16[short_ids[k]]
+                jobs.append((y, None if len(set(bl)) == 1 else bl, None, [keys[short_ids[k]] for k in bucket], ("short", [short_ids[k] for k in bucket])))
+            # ---- run: one enhance_batch per job, one after the other or in lockstep
+            if grouped and self._has_sampler and len(jobs) > 1:
+                outs = self.enhance_stream([(j[0], j[1]) for j in jobs], width=8 if grouped is True else int(grouped), row_seeds=[j[3] for j in jobs],
+                                           peaks=[j[2] for j in jobs], **sampler_kwargs)
+                res = [(x, int(n_eval) * x.shape[0]) for x, n_eval in zip(outs, self.last_nfev_stream)]
+            else:
+                res = []
+                for j in jobs:
+                    self.last_nfev_rows = None
+                    x, n_eval = self.enhance_batch(j[0], lengths=j[1], peak=j[2], row_seeds=j[3], return_nfe=True, **sampler_kwargs)
+                    own = getattr(self, "last_nfev_rows", None)       # (ODE: every row's own count; otherwise all rows take n_eval)
+                    res.append((x, sum(int(v) for v in own) if own else int(n_eval) * x.shape[0]))
+            pool = torch.zeros((max(len(entries), 1), W), dtype=torch.float32, device=self.device)
+            result, nfe = [None] * R, 0
+            for (y, bl, _, _, (kind, where)), (x, evals) in zip(jobs, res):
+                nfe += evals
+                if kind == "pool":
+                    pool[where:where + y.shape[0]] = x
+                else:
+                    for row, i in enumerate(where):
+                        result[i] = x[row, :x16[i].numel()].clone()
+            # ---- the stitch: all long recordings in one launch
+            if long_ids:
+                stitched = ops.crossfade_rows(pool, win_row, [x16[i].numel() for i in long_ids], rec_windows, W, V,
+                                              ramp=ops.crossfade_ramp(V, ramp, self.device))
+                for r, i in enumerate(long_ids):
+                    result[i] = stitched[r, :x16[i].numel()]
+            for i in range(R):
+                if self._off_rate(rates[i]):
+                    result[i] = dm.resample(result[i].contiguous(), dm.sample_rate, int(rates[i]))[:counts[i]]
+        return (result, nfe) if return_nfe else result
 
     @staticmethod
     def _slice_keys(kwargs, sl):
@@ -337,7 +470,7 @@ class ScoreModel(_Base):
         return self._sampler_minibatched(lambda sl: sampling.get_ode_sampler(sde, self, y=y[sl], **self._slice_keys(kwargs, sl)), y, minibatch)
 
     def enhance_batch(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", N=50,
-                      corrector_steps=1, snr=0.5, return_nfe=False, lengths=None, row_seeds=None, sr=None, **kwargs):
+                      corrector_steps=1, snr=0.5, return_nfe=False, lengths=None, row_seeds=None, sr=None, peak=None, **kwargs):
         """B equal-length utterances y [B, L] in one sampler run.  Every op on the path is per utterance, the Langevin
         corrector runs with per-row step sizes and the ODE sampler with one Runge-Kutta step controller per row (the
         reference solves one utterance per solve_ivp call), so with INJECTED noise (noise_fn) row b equals enhance(y[b:b+1])
@@ -351,14 +484,15 @@ class ScoreModel(_Base):
         (storm_amd.distributed.bucket_by_frames); y is zero filled to the longest row and so is the result.
         sr: the sample rate of y (and of lengths) when it is not the model's 16 kHz - y is resampled to 16 kHz on the device, enhanced as
         a 16 kHz batch, resampled back and every row trimmed to its input sample count; the padded-frame rule of a ragged batch then
-        holds for the 16 kHz lengths."""
+        holds for the 16 kHz lengths.
+        peak: fp32 [B], the rows' normalisation factors instead of their own peaks (None: as the reference, every row's own peak)."""
         if self._off_rate(sr):
             y16, l16 = self._to_model_rate(y, sr, lengths)
             x16, nfe = self.enhance_batch(y16, sampler_type, predictor, corrector, N, corrector_steps, snr, return_nfe=True, lengths=l16,
-                                          row_seeds=row_seeds, **kwargs)
+                                          row_seeds=row_seeds, peak=peak, **kwargs)
             x_hat = self._from_model_rate(x16, sr, l16, lengths, y.shape[1])
             return (x_hat, nfe) if return_nfe else x_hat
-        Y, peak, T_orig = self._prepare(y, lengths)
+        Y, peak, T_orig = self._prepare(y, lengths, peak)
         if row_seeds is not None:
             kwargs["row_seeds"] = row_seeds
         if sampler_type == "pc":
@@ -460,6 +594,24 @@ class DiscriminativeModel(ScoreModel):
                 rows = ops.pair_loss_rows(x, x_hat, kind=self.loss_type, frames=frames)
         return torch.mean(rows) if reduce else rows
 
+    _has_sampler = False                 # (enhance_long: no noise keys, no grouped sampler stream)
+
+    def enhance_batch(self, y, lengths=None, peak=None, sr=None, return_nfe=False, **ignored_kwargs):
+        """The batched form of `enhance`: y [B, L] -> fp32 [B, L] on the device, row b equal to enhance(y[b:b+1]).  lengths, peak and sr as
+        in ScoreModel.enhance_batch; sampler keywords (row_seeds among them) are ignored, as `enhance` ignores them.  return_nfe: the one
+        network evaluation."""
+        if self._off_rate(sr):
+            y16, l16 = self._to_model_rate(y, sr, lengths)
+            x_hat = self._from_model_rate(self.enhance_batch(y16, lengths=l16, peak=peak), sr, l16, lengths, y.shape[1])
+            return (x_hat, 1) if return_nfe else x_hat
+        with torch.no_grad():
+            Y, peak, T_orig = self._prepare(y, lengths, peak)
+            X_hat = self(Y)
+            if getattr(self.dnn, "FORCE_STFT_OUT", False):    # a time-domain net: its waveforms go back to spectrograms (model.py:362-363)
+                X_hat = self._forward_transform(self._stft(X_hat.reshape(X_hat.shape[0], -1))).unsqueeze(1)
+            x_hat = self.data_module.spec_to_wav(X_hat, T_orig, peak, lengths=lengths)
+        return (x_hat, 1) if return_nfe else x_hat
+
     def enhance(self, y, sr=None, **ignored_kwargs):
         """sr: y's sample rate when it is not 16 kHz - resampled on the device before and after, as in ScoreModel.enhance_batch"""
         if self._off_rate(sr):
@@ -558,18 +710,19 @@ class StochasticRegenerationModel(_Base):
 
     def enhance_batch(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="none", N=30,
                       corrector_steps=1, snr=0.5, denoiser_only=False, return_nfe=False, return_stft=False, lengths=None,
-                      row_seeds=None, sr=None, **kwargs):
+                      row_seeds=None, sr=None, peak=None, **kwargs):
         """row_seeds: one Philox key per row, as in ScoreModel.enhance_batch (row b draws what its batch-1 run with seed = s_b draws);
-        sr: the sample rate of y and lengths when it is not 16 kHz, as there (return_stft=True returns the 16 kHz spectrograms)"""
+        sr: the sample rate of y and lengths when it is not 16 kHz, as there (return_stft=True returns the 16 kHz spectrograms);
+        peak: fp32 [B], the rows' normalisation factors instead of their own peaks, as there"""
         if self._off_rate(sr):
             y16, l16 = self._to_model_rate(y, sr, lengths)
             out = self.enhance_batch(y16, sampler_type, predictor, corrector, N, corrector_steps, snr, denoiser_only=denoiser_only,
-                                     return_nfe=True, return_stft=return_stft, lengths=l16, row_seeds=row_seeds, **kwargs)
+                                     return_nfe=True, return_stft=return_stft, lengths=l16, row_seeds=row_seeds, peak=peak, **kwargs)
             if return_stft:
                 return out
             x_hat = self._from_model_rate(out[0], sr, l16, lengths, y.shape[1])
             return (x_hat, out[1]) if return_nfe else x_hat
-        Y, peak, T_orig = self._prepare(y, lengths)
+        Y, peak, T_orig = self._prepare(y, lengths, peak)
         kwargs.setdefault("langevin_per_row", True)
         if row_seeds is not None:
             kwargs["row_seeds"] = row_seeds

@@ -704,11 +704,15 @@ def _row_len(lengths, like):
     return torch.tensor([int(v) for v in lengths], dtype=torch.int32, device=like.device)
 
 
+PEAK_FLOOR = 1e-20                       # storm_peak_abs never returns less (as fp32): the peak of a row whose every sample is zero
+
+
 def peak_abs(wav, lengths=None):
+    """fp32 [B]: max |wav[b]| of a batch whose rows are contiguous (the rows may overlap: a strided view), at least PEAK_FLOOR"""
     B, Lw = wav.shape
     out = _alloc((B,), torch.float32, wav)
     rl = _row_len(lengths, wav)
-    L.check(L.lib().storm_peak_abs(L.ptr(wav), L.ptr(out), B, Lw, wav.stride(0), L.ptr(rl), L.stream()), "storm_peak_abs")
+    L.check(L.lib().storm_peak_abs(L.ptr_rows(wav), L.ptr(out), B, Lw, wav.stride(0), L.ptr(rl), L.stream()), "storm_peak_abs")
     return out
 
 
@@ -728,7 +732,7 @@ def stft(wav, peak=None, n_fft=510, hop=128, spec_factor=1.0, spec_abs_exponent=
     win, tw = dft_tables(n_fft, wav.device, window)
     spec = torch.empty((B, n_fft // 2 + 1, Tpad), dtype=torch.complex64, device=wav.device)
     rl = _row_len(lengths, wav)
-    L.check(L.lib().storm_stft(L.ptr(wav), L.ptr(peak), L.ptr(_r(spec)), L.ptr(win), L.ptr(tw), B, Lw, wav.stride(0),
+    L.check(L.lib().storm_stft(L.ptr_rows(wav), L.ptr(peak), L.ptr(_r(spec)), L.ptr(win), L.ptr(tw), B, Lw, wav.stride(0),
                                n_fft, hop, n_frames, Tpad, float(spec_factor), float(spec_abs_exponent), L.ptr(rl), L.stream()),
             "storm_stft")
     return spec
@@ -812,6 +816,94 @@ def resample_poly(x, up, down, lengths=None):
     L.check(L.lib().storm_resample_poly(L.ptr_rows(x), L.ptr(y), L.ptr(taps), B, Lin, stride, Lout, y.stride(0), L.ptr(rl), up, down,
                                         L.stream()), "storm_resample_poly")
     return y
+
+
+# ---------------------------------------------------------------- long recordings ---------
+CROSSFADE_TILE = L.CROSSFADE_TILE        # outputs per workgroup of storm_crossfade_rows (tests place lengths around it)
+WINDOW_KEY_STEP = 0x9E3779B97F4A7C15     # window k of a recording draws from key + (k + 1) * this, mod 2^63
+_ramps = {}
+
+
+def _check_overlap(W, V):
+    W, V = int(W), int(V)
+    if W < 2 or V < 1 or V > W // 2:
+        raise ValueError(f"V={V} lies outside [1, W // 2] for windows of W={W} samples")
+    return W, V
+
+
+def window_plan(n_samples, W, V):
+    """(n, padded_length) of a recording of n_samples: n = ceil((n_samples - V) / H) windows of W samples at hop H = W - V, the [n, W]
+    view of stride H of the recording zero filled to padded_length = (n - 1) H + W.  A recording of at most W samples is not windowed:
+    (1, n_samples)."""
+    W, V = _check_overlap(W, V)
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError(f"window_plan: a recording of {n_samples} samples")
+    if n_samples <= W:
+        return 1, n_samples
+    H = W - V
+    n = -(-(n_samples - V) // H)
+    return n, (n - 1) * H + W
+
+
+def window_key(key, k):
+    """the Philox key of window k of a recording with key `key`: (key + (k + 1) * 0x9E3779B97F4A7C15) mod 2^63"""
+    return (int(key) + (int(k) + 1) * WINDOW_KEY_STEP) % 2 ** 63
+
+
+def crossfade_ramp(V, kind="hann", device="cpu"):
+    """The fade-in weights of a V-sample overlap as storm_crossfade_rows reads them: fp32 [V] on `device`, designed by the library in fp64
+    and rounded once (storm_crossfade_ramp) - 'hann': sin(pi/2 (j + 1) / (V + 1))^2, 'linear': (j + 1) / (V + 1).  Cached per device."""
+    V = int(V)
+    if V < 1:
+        raise ValueError(f"V={V}: an overlap has at least one sample")
+    if kind not in L.RAMP_KINDS:
+        raise ValueError(f"ramp {kind!r}: one of {sorted(L.RAMP_KINDS)}")
+    key = (V, kind, str(torch.device(device)))
+    if key not in _ramps:
+        host = torch.empty(V, dtype=torch.float32)
+        L.check(L.lib().storm_crossfade_ramp(V, L.RAMP_KINDS[kind], host.data_ptr()), "storm_crossfade_ramp")
+        _ramps[key] = host.to(device)
+    return _ramps[key]
+
+
+def crossfade_rows(pool, win_row, rec_len, rec_windows, W, V, ramp=None, width=None):
+    """The stitch of R recordings in ONE launch (storm_crossfade_rows).  pool: the enhanced windows, fp32 [N, W] (row stride may exceed W);
+    win_row: the pool row of every window in (recording, window) order, -1 for a skipped window (it reads as zeros); rec_len / rec_windows:
+    every recording's sample count and window count (host ints: rec_windows[r] = window_plan(rec_len[r], W, V)[0]); ramp: fp32 [V] on the
+    pool's device (None: crossfade_ramp(V)).  Returns fp32 [R, width] (width None: the longest recording), zero past a recording's length."""
+    W, V = _check_overlap(W, V)
+    if pool.dim() != 2 or pool.dtype != torch.float32 or pool.shape[1] != W or pool.shape[0] < 1 or pool.stride(1) != 1:
+        raise ValueError(f"pool: expected float32 rows [N, W = {W}], got {pool.dtype} {tuple(pool.shape)}")
+    N = pool.shape[0]
+    win_row, rec_len, rec_windows = [int(v) for v in win_row], [int(v) for v in rec_len], [int(v) for v in rec_windows]
+    R, H = len(rec_len), W - V
+    if R < 1 or len(rec_windows) != R:
+        raise ValueError(f"rec_windows has {len(rec_windows)} entries for {R} recordings in rec_len")
+    for r, (n_samples, n) in enumerate(zip(rec_len, rec_windows)):
+        if n < 1 or n_samples < 1 or n_samples > (n - 1) * H + W or (n > 1 and n_samples <= (n - 1) * H + V):
+            raise ValueError(f"rec_len[{r}] = {n_samples} samples is inconsistent with rec_windows[{r}] = {n} windows of {W} at hop {H}")
+    if len(win_row) != sum(rec_windows):
+        raise ValueError(f"win_row has {len(win_row)} entries for {sum(rec_windows)} windows in rec_windows")
+    if any(v < -1 or v >= N for v in win_row):
+        raise ValueError(f"win_row names a row outside the pool of {N} rows (-1 marks a skipped window): {[v for v in win_row if v < -1 or v >= N][:4]}")
+    width = max(rec_len) if width is None else int(width)
+    if width < max(rec_len):
+        raise ValueError(f"width={width} is narrower than the longest recording ({max(rec_len)} samples)")
+    if ramp is None:
+        ramp = crossfade_ramp(V, "hann", pool.device)
+    if ramp.dtype != torch.float32 or tuple(ramp.shape) != (V,) or ramp.device != pool.device:
+        raise ValueError(f"ramp: expected float32 [V = {V}] on {pool.device}, got {ramp.dtype} {tuple(ramp.shape)} on {ramp.device}")
+    first = [0] * R
+    for r in range(1, R):
+        first[r] = first[r - 1] + rec_windows[r - 1]
+    table = torch.tensor(rec_len + rec_windows + first + win_row, dtype=torch.int32).to(pool.device)       # one upload for the four arrays
+    lens, wins, firsts, rows = table[:R], table[R:2 * R], table[2 * R:3 * R], table[3 * R:]
+    out = torch.empty((R, width), dtype=torch.float32, device=pool.device)
+    stride = pool.stride(0) if N > 1 else W                      # (a one-row tensor's row stride is whatever its producer left there)
+    L.check(L.lib().storm_crossfade_rows(L.ptr_rows(pool), N, stride, L.ptr(out), R, width, out.stride(0), L.ptr(lens), L.ptr(wins), L.ptr(firsts),
+                                         L.ptr(rows), W, V, L.ptr(ramp.contiguous()), L.stream()), "storm_crossfade_rows")
+    return out
 
 
 # ---------------------------------------------------------------- metrics -----------------
