@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Score a directory of enhanced files against the clean and noisy ones - the reference's calc_metrics step on the device:
 
-    python calc_metrics.py --clean_dir clean/ --noisy_dir noisy/ --enhanced_dir out/ [--batch 16] [--resample]
+    python calc_metrics.py --clean_dir clean/ --noisy_dir noisy/ --enhanced_dir out/ [--batch 16] [--resample] [--stoi]
 
 Files are matched by basename (every *.wav of --enhanced_dir needs its clean and noisy namesake).  Each triple is trimmed to its
 shortest member, the triples are bucketed by frame count and scored as ragged micro-batches (storm_amd.util.inference.score_batch:
@@ -9,10 +9,13 @@ SI-SDR / SI-SIR / SI-SAR, LSD and the input SNR, util/other.py:16-44, 96-100); P
 / `pystoi` packages import.  Written into --enhanced_dir:
 
     _results.csv       Filename,Length,iSNR,si_sdr,si_sir,si_sar,lsd[,pesq,estoi] - one line per file, Length in samples at 16 kHz
+                       (--stoi: ...,lsd[,pesq],stoi,estoi)
     _avg_results.txt   metric: mean ± std of each column (mean_std, NaNs dropped)
 
 A file's line does not depend on --batch nor on the other files.  --resample: files of other rates are resampled to 16 kHz on the
-device when they are loaded (SpecsDataModule.resample); without it such a file is refused, as in enhancement.py."""
+device when they are loaded (SpecsDataModule.resample); without it such a file is refused, as in enhancement.py.  --stoi: STOI and ESTOI
+of every file on the device, in the same micro-batches (storm_stoi_rows, defined in include/storm_hip.h and checked against a restatement
+of the published algorithm, not against pystoi); host pystoi is then not called, and a pesq column still appears when `pesq` imports."""
 import glob
 import os
 from argparse import ArgumentParser
@@ -34,6 +37,7 @@ def main():
     p.add_argument("--enhanced_dir", type=str, required=True, help="Directory of the enhanced files; the results are written here.")
     p.add_argument("--batch", type=int, default=16, help="files per scoring micro-batch")
     p.add_argument("--resample", action="store_true", help="read files of any sample rate: each is resampled to 16 kHz on the device when it is loaded")
+    p.add_argument("--stoi", action="store_true", help="append the columns stoi,estoi, computed on the device (pystoi is not needed and not called)")
     args = p.parse_args()
 
     from storm_amd import distributed as D
@@ -55,20 +59,27 @@ def main():
         n = min(x.shape[0], y.shape[0], e.shape[0])
         triples.append((x[:n], y[:n], e[:n]))
     lengths = [t[0].shape[0] for t in triples]
-    values = {c: [None] * len(names) for c in COLUMNS}
+    device_columns = COLUMNS + (("stoi", "estoi") if args.stoi else ())
+    values = {c: [None] * len(names) for c in device_columns}
     for ids in D.bucket_by_frames(lengths, args.batch):
         lens = [lengths[i] for i in ids]
         rows = torch.zeros(3, len(ids), max(lens), device=dev)
         for k, i in enumerate(ids):
             for j in range(3):
                 rows[j, k, :lens[k]] = triples[i][j]
-        scores = {k: v.cpu() for k, v in score_batch(rows[0], rows[1], rows[2], lengths=lens).items()}
+        kw = dict(stoi=True, fs=SR) if args.stoi else {}
+        scores = {k: v.cpu() for k, v in score_batch(rows[0], rows[1], rows[2], lengths=lens, **kw).items()}
         for k, i in enumerate(ids):
-            for c in COLUMNS:
-                values[c][i] = float(scores[KEYS[c]][k])
+            for c in device_columns:
+                values[c][i] = float(scores[KEYS.get(c, c)][k])
     columns = list(COLUMNS)
     pesq, stoi = _optional("pesq", "pesq"), _optional("pystoi", "stoi")
-    if pesq is not None and stoi is not None:
+    if args.stoi:
+        if pesq is not None:
+            columns += ["pesq"]
+            values["pesq"] = [pesq(SR, x.cpu().numpy(), e.cpu().numpy(), "wb") for x, _, e in triples]
+        columns += ["stoi", "estoi"]
+    elif pesq is not None and stoi is not None:
         columns += ["pesq", "estoi"]
         values["pesq"] = [pesq(SR, x.cpu().numpy(), e.cpu().numpy(), "wb") for x, _, e in triples]
         values["estoi"] = [stoi(x.cpu().numpy(), e.cpu().numpy(), SR, extended=True) for x, _, e in triples]

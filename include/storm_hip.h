@@ -528,6 +528,50 @@ int storm_lsd_rows(const float* spec_hat, const float* spec, double* out, void* 
                    const int* row_frames, double eps, storm_stream_t st);
 
 /* ------------------------------------------------------------------------------------------
+ * Intelligibility of enhanced audio: STOI (Taal, Hendriks, Heusdens, Jensen 2011) and ESTOI (Jensen, Taal 2016) per row.  The reference
+ * never computes them itself (it calls the pystoi package, util/inference.py:65), so THIS TEXT is the specification; the numbers were
+ * checked against a float64 restatement of the published algorithm (tests/stoi_cases.py), not against pystoi.
+ * Constants: FS = 10000, N_FRAME = 256, HOP = 128, NFFT = 512, 15 third-octave bands from 150 Hz, segments of N = 30 frames,
+ * BETA = -15 dB, DYN_RANGE = 40 dB, EPS = 2^-52.  Inputs: x (clean) and y (processed), the row's first `len` samples of each, at fs_sig.
+ *  1. Resample (only if fs_sig != FS) both signals by up / down = FS / fs_sig reduced: R = max(up, down), fc = 1 / (2 R),
+ *     L = ceil((60 - 8) / (28.714 fc / 10)); h[t], t = 0 .. 2 L: kaiser(2 L + 1, beta = 0.1102 (60 - 8.7))[t] * 2 up fc sinc(2 fc (t - L)),
+ *     normalised to sum(h) = 1, applied as scipy.signal.resample_poly(x, up, down, window=h) applies it (times up, centred:
+ *     out[n] = sum_k up h[n down - k up + L] in[k]); ceil(len up / down) outputs.  16 kHz: 5 / 8, 581 taps; 48 kHz: 5 / 24, 1741 taps.
+ *  2. Silent frames: w = hanning(258)[1:-1]; frames start at i = 0, 128, ... < len - 256 (strict: the frame that would end exactly at the
+ *     last sample is not taken); e_k = 20 log10(|w x_frame_k|_2 + EPS); frame k is kept iff max_k(e) - 40 - e_k < 0, and the same mask applies
+ *     to y.  The K kept frames, already windowed, are overlap-added at hop 128 into x_sil, y_sil of (K - 1) 128 + 256 samples.
+ *  3. STFT: frames of x_sil start at 0, 128, ... < len_sil - 256: M = K - 1 frames; each times w again, zero padded to 512, rfft (257 bins).
+ *  4. Bands: band i sums |X_j|^2 over edge_i <= j < edge_{i+1}, edges (7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219)
+ *     (the bins nearest to 150 * 2^((2 i -+ 1) / 6) Hz); X_tob = sqrt(band sums) [15][M], likewise Y_tob.
+ *  5. M < 30 (rows with len <= 256 included): both results are 1e-5 (pystoi's "not enough frames" value).
+ *  6. Segments m = 30 .. M: columns m - 30 .. m - 1, J = M - 29 segments of [15][30].
+ *  ESTOI: in each segment, every band minus its mean over the 30 frames, over its 2-norm; then every frame minus its mean over the 15
+ *     bands, over its 2-norm; for X and Y; d = sum(Xn Yn) / (30 J).
+ *  STOI: in each segment and band c = |x| / (|y| + EPS), y' = min(c y, x (1 + 10^(15/20))); x and y' minus their means over the 30 frames,
+ *     each over its norm + EPS; d = sum(x y') / (15 J).
+ *  Deviation from pystoi: pystoi adds EPS * randn jitter before each ESTOI normalisation (its last digits are not deterministic); here
+ *     there is no jitter and every ESTOI normalisation divides by norm + EPS - a constant band or frame contributes 0, not a random direction.
+ *
+ * storm_stoi_num_taps / storm_stoi_taps (host): the filter of step 1 for fs_sig, 2 L + 1 taps (< 0: refused - fs_sig < 1 or
+ *   max(up, down) > STORM_RESAMPLE_MAX_RATE), designed in fp64 (I0 by its power series), times up, rounded to fp32 once, written in
+ *   storm_resample_taps' phase-major layout fp32 [up][M], M = ceil(num_taps / up), into the CALLER's host memory.
+ * storm_resample_poly_taps: storm_resample_poly with a table of an explicit num_taps (odd, >= 1; half = (num_taps - 1) / 2) - the same
+ *   kernel, the same single fp32 FMA chain per output.
+ * storm_stoi_rows: x, y fp32 [B][L] AT 10 kHz (row strides in floats) -> out fp64 [B][2] = (STOI, ESTOI), steps 2 - 6.  row_len (optional,
+ *   device int32 [B]): row b is its first row_len[b] samples, the rest is never read.  After the samples are read all arithmetic is fp64;
+ *   no atomics, every sum in an order fixed by indices inside the row: a row's two numbers are the same bits alone, in any batch, at any
+ *   batch width, row stride and position.  x_sil is never written: spectrogram frame m reads the kept frames m - 1, m, m + 1 of the row.
+ *   scratch: at least storm_stoi_scratch_bytes(B, L) bytes of device memory, 8-byte aligned; after the call it begins with int32 [B][4] =
+ *   (gate frames, kept frames K, segments J, spectrogram frames M) of every row. */
+int storm_stoi_num_taps(int fs_sig);
+int storm_stoi_taps(int fs_sig, float* taps_phase_major, long long capacity);
+int storm_resample_poly_taps(const float* x, float* y, const float* taps, int B, long long L_in, long long stride_in, long long L_out,
+                             long long stride_out, const int* row_len, int up, int down, int num_taps, storm_stream_t s);
+long long storm_stoi_scratch_bytes(int B, long long L);
+int storm_stoi_rows(const float* x, const float* y, double* out, void* scratch, long long scratch_bytes, int B, long long L,
+                    long long stride_x, long long stride_y, const int* row_len, storm_stream_t st);
+
+/* ------------------------------------------------------------------------------------------
  * Long recordings: a recording longer than one window of W samples is enhanced as n overlapping windows (overlap V, 1 <= V <= W / 2, hop
  * H = W - V, window k starts at k H, n = ceil((L - V) / H)) and stitched back.  Output sample m < L of a recording:
  *   k = min(m / H, n - 1), j = m - k H, cur = window_k[j];

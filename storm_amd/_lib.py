@@ -152,6 +152,11 @@ _SIGNATURES = {
     "storm_energy_ratios_rows": ([_vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _ll, _vp, _vp], C.c_int),
     "storm_lsd_scratch_bytes": ([_i, _i, _i], C.c_longlong),
     "storm_lsd_rows": ([_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, C.c_double, _vp], C.c_int),
+    "storm_stoi_num_taps": ([_i], C.c_int),
+    "storm_stoi_taps": ([_i, _vp, _ll], C.c_int),
+    "storm_resample_poly_taps": ([_vp, _vp, _vp, _i, _ll, _ll, _ll, _ll, _vp, _i, _i, _i, _vp], C.c_int),
+    "storm_stoi_scratch_bytes": ([_i, _ll], C.c_longlong),
+    "storm_stoi_rows": ([_vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _vp, _vp], C.c_int),
     "storm_crossfade_ramp": ([_i, _i, _vp], C.c_int),
     "storm_crossfade_rows": ([_vp, _i, _ll, _vp, _i, _ll, _ll, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp], C.c_int),
     "storm_tasnet_num_partials":([_i, _i, _i], C.c_int),

@@ -342,5 +342,8 @@ extern "C" int storm_resample_poly(const float* x, float* y, const float* taps, 
 // ---- evaluation metrics of enhanced audio (storm_energy_ratios_rows, storm_lsd_rows): kernels and entry points ----
 #include "metrics.h"
 
+// ---- intelligibility (storm_stoi_rows, storm_stoi_taps, storm_resample_poly_taps): STOI / ESTOI kernels, filter design and entry points ----
+#include "stoi.h"
+
 // ---- long recordings (storm_crossfade_rows, storm_crossfade_ramp): the stitch of enhanced windows, kernel and entry points ----
 #include "longform.h"

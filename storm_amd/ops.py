@@ -958,6 +958,83 @@ def lsd_rows(S_hat, S, frames=None, eps=1e-10):
     return out
 
 
+# ---------------------------------------------------------------- intelligibility ---------
+STOI_FS = 10000                          # the rate STOI / ESTOI are defined at (include/storm_hip.h: storm_stoi_rows)
+_stoi_tables = {}
+
+
+def _stoi_table(fs, device):
+    """(taps [up, M] on `device`, num_taps, up, down) of the STOI resampling filter fs -> 10 kHz: designed by the library (storm_stoi_taps),
+    fetched once per rate and device"""
+    key = (fs, str(device))
+    if key not in _stoi_tables:
+        n = L.lib().storm_stoi_num_taps(fs)
+        if n < 0:
+            L.check(n, "storm_stoi_num_taps")
+        up, down = resample_ratio(STOI_FS, fs)
+        host = torch.empty((up, -(-n // up)), dtype=torch.float32)
+        L.check(L.lib().storm_stoi_taps(fs, host.data_ptr(), host.numel()), "storm_stoi_taps")
+        _stoi_tables[key] = (host.to(device), n, up, down)
+    return _stoi_tables[key]
+
+
+def stoi_taps(fs, device="cpu"):
+    """The library's STOI resampling filter fs -> 10 kHz as its kernel reads it: fp32 [up, M], T[p][m] = up h[p + m up], zero past the
+    phase's last tap (include/storm_hip.h: storm_stoi_taps).  A copy: the cached table stays as the library wrote it."""
+    return _stoi_table(int(fs), torch.device(device))[0].clone()
+
+
+def stoi_resample(x, fs, lengths=None):
+    """x [B, L] fp32 at `fs` -> [B, ceil(L up / down)] at 10 kHz through the STOI filter (storm_resample_poly_taps); rows past their
+    length are zero, as in resample_poly.  fs = 10000 returns x itself (no launch)."""
+    fs = int(fs)
+    if fs == STOI_FS:
+        return x
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"stoi_resample: expected a float32 batch [B, L], got {x.dtype} {tuple(x.shape)}")
+    taps, n, up, down = _stoi_table(fs, x.device)
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    B, Lin = x.shape
+    Lout = -(-Lin * up // down)
+    y = torch.empty((B, Lout), dtype=torch.float32, device=x.device)
+    rl = _row_len(lengths, x)
+    stride = x.stride(0) if B > 1 else Lin                       # (a one-row tensor's row stride is whatever its producer left there)
+    L.check(L.lib().storm_resample_poly_taps(L.ptr_rows(x), L.ptr(y), L.ptr(taps), B, Lin, stride, Lout, y.stride(0), L.ptr(rl), up, down, n,
+                                             L.stream()), "storm_resample_poly_taps")
+    return y
+
+
+def stoi_rows(clean, estimate, lengths=None, fs=16000, counts=False):
+    """fp64 [B, 2] = (STOI, ESTOI) per row of two fp32 waveform batches [B, L] at `fs` (rows may be strided views): the definition of
+    include/storm_hip.h (storm_stoi_rows), 1e-5 for a row with fewer than 30 spectrogram frames.  Unless fs is 10000 both batches are
+    resampled on the device first (storm_resample_poly_taps with the STOI filter; row b then has ceil(lengths[b] up / down) samples).
+    lengths: per-row sample counts of a ragged batch (the rest of a row is not read).  A row's numbers do not depend on the batch it is in.
+    counts=True (tests): also int32 [B, 3] = the row's gate frames, kept frames and segments."""
+    for name, x in (("clean", clean), ("estimate", estimate)):
+        if x.dim() != 2 or x.dtype != torch.float32 or x.shape != clean.shape:
+            raise ValueError(f"stoi_rows: {name} is {x.dtype} {tuple(x.shape)}, expected float32 [B, L] = {tuple(clean.shape)}")
+    B, Lw = clean.shape
+    if B < 1 or Lw < 1:
+        raise ValueError(f"stoi_rows: empty batch {tuple(clean.shape)}")
+    _metric_lengths("stoi_rows", lengths, B, Lw, "lengths")
+    fs = int(fs)
+    if fs != STOI_FS:
+        up, down = resample_ratio(STOI_FS, fs)
+        clean, estimate = stoi_resample(clean, fs, lengths), stoi_resample(estimate, fs, lengths)
+        if lengths is not None:
+            lengths = [-(-int(v) * up // down) for v in lengths]
+        Lw = clean.shape[1]
+    rows = [x if x.stride(1) == 1 else x.contiguous() for x in (clean, estimate)]
+    strides = [x.stride(0) if B > 1 else Lw for x in rows]       # (a one-row tensor's row stride is whatever its producer left there)
+    out = _alloc((B, 2), torch.float64, clean)
+    ws = torch.empty((L.lib().storm_stoi_scratch_bytes(B, Lw) // 4,), dtype=torch.int32, device=clean.device)
+    rl = _row_len(lengths, clean)
+    L.check(L.lib().storm_stoi_rows(L.ptr_rows(rows[0]), L.ptr_rows(rows[1]), L.ptr(out), L.ptr(ws), 4 * ws.numel(), B, Lw, strides[0],
+                                    strides[1], L.ptr(rl), L.stream()), "storm_stoi_rows")
+    return (out, ws[:4 * B].reshape(B, 4)[:, :3].clone()) if counts else out
+
+
 # ---------------------------------------------------------------- ConvTasNet --------------
 TASNET_ENCODE, TASNET_POINTWISE, TASNET_DEPTHWISE = 0, 1, 2
 

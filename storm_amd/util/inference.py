@@ -34,24 +34,33 @@ def _optional(name, attr):
 METRIC_KEYS = ("si_sdr", "si_sir", "si_sar", "lsd", "isnr")
 
 
-def score_batch(clean, noisy, estimate, lengths=None):
+def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000):
     """The calc_metrics numbers of one micro-batch of device waveforms [B, L]: a dict of fp64 [B] tensors si_sdr / si_sir / si_sar
     (energy_ratios(estimate, clean, noisy - clean), util/other.py:35-44), lsd (estimate against clean, :16-19) and isnr (snr_dB(clean,
     noisy - clean), :96-100).  lengths: per-row sample counts of a ragged batch.  One energy launch pair, two STFTs and one LSD launch
-    pair; every row's numbers are those of its own one-row call."""
+    pair; every row's numbers are those of its own one-row call.  stoi=True adds the keys stoi and estoi: ops.stoi_rows(clean, estimate)
+    of waveforms at `fs` Hz (resampled to 10 kHz on the device; include/storm_hip.h has the definition)."""
     from .. import ops
     clean, noisy, estimate = clean.float(), noisy.float(), estimate.float()
     r = ops.energy_ratios_rows(estimate, clean, noisy - clean, lengths=lengths)
-    return {"si_sdr": r[:, 0], "si_sir": r[:, 1], "si_sar": r[:, 2], "lsd": lsd(estimate, clean, lengths=lengths), "isnr": r[:, 3]}
+    out = {"si_sdr": r[:, 0], "si_sir": r[:, 1], "si_sar": r[:, 2], "lsd": lsd(estimate, clean, lengths=lengths), "isnr": r[:, 3]}
+    if stoi:
+        d = ops.stoi_rows(clean, estimate, lengths=lengths, fs=fs)
+        out["stoi"], out["estoi"] = d[:, 0], d[:, 1]
+    return out
 
 
 def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminative=False, pairs=None, batch=16, noise_for=None,
-                   metrics=False, **enhance_kwargs):
+                   metrics=False, estoi=None, **enhance_kwargs):
     """Returns (pesq, si_sdr, estoi, [noisy, estimate, clean spectrograms] | None, [noisy, estimate, clean audio] | None),
     the reference's tuple.  `discriminative` is accepted for signature parity (the model class decides the path).
     noise_for(ids) -> noise_fn: injected sampler noise for the micro-batch of files `ids` (parity tests; production runs
     pass seed= and draw in-kernel).  metrics=True appends a sixth element: the means over the evaluated files of score_batch's
-    numbers, {si_sdr, si_sir, si_sar, lsd, isnr} as floats, computed on the same micro-batches."""
+    numbers, {si_sdr, si_sir, si_sar, lsd, isnr} as floats, computed on the same micro-batches.
+    estoi="device": the third element is the mean over the files of the device ESTOI (ops.stoi_rows at 16 kHz, one call per micro-batch),
+    whether or not pystoi imports, and the sixth element gains the means stoi and estoi; None: pystoi on the host, NaN without it."""
+    if estoi not in (None, "device"):
+        raise ValueError(f"estoi={estoi!r}: None (pystoi on the host) or 'device'")
     model.eval()
     pesq, stoi = _optional("pesq", "pesq"), _optional("pystoi", "stoi")
     if pairs is None:
@@ -63,6 +72,7 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
     est = [None] * n
     sdr = torch.zeros(n, dtype=torch.float64)
     scores = {k: torch.zeros(n, dtype=torch.float64) for k in METRIC_KEYS} if metrics else None
+    intel = torch.zeros(n, 2, dtype=torch.float64) if estoi == "device" else None
     hop = model.data_module.hop_length
     batched = hasattr(model, "enhance_batch") and not discriminative
     for ids in bucket_by_frames([p[1].shape[-1] for p in pairs], batch if batched else 1, hop=hop):
@@ -91,12 +101,18 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
             w = min(width, x_hat.shape[1])
             for key, v in score_batch(x[:, :w], y[:, :w], x_hat[:, :w], lengths=[min(v, w) for v in lens]).items():
                 scores[key][ids] = v.cpu()
+        if intel is not None:
+            from .. import ops
+            w = min(width, x_hat.shape[1])
+            intel[ids] = ops.stoi_rows(x[:, :w], x_hat[:, :w], lengths=[min(v, w) for v in lens], fs=16000).cpu()
         for k, i in enumerate(ids):
             est[i] = x_hat[k, :lens[k]].cpu()
     _pesq = _estoi = float("nan")
     if pesq is not None:
         _pesq = sum(pesq(16000, pairs[i][0][0].numpy(), est[i].numpy(), "wb") for i in range(n)) / n
-    if stoi is not None:
+    if intel is not None:
+        _estoi = float(intel[:, 1].mean()) if n else math.nan
+    elif stoi is not None:
         _estoi = sum(stoi(pairs[i][0][0].numpy(), est[i].numpy(), 16000, extended=True) for i in range(n)) / n
     specs = audios = None
     if spec:
@@ -109,6 +125,8 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
     out = (_pesq, float(sdr.mean()) if n else math.nan, _estoi, specs, audios)
     if metrics:
         out += ({k: float(v.mean()) if n else math.nan for k, v in scores.items()},)
+        if intel is not None:
+            out[5].update(stoi=float(intel[:, 0].mean()) if n else math.nan, estoi=float(intel[:, 1].mean()) if n else math.nan)
     return out
 
 

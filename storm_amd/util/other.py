@@ -1,6 +1,9 @@
 """Small utilities of sgmse/util/other.py that the hot path and the evaluation loop use:
 pad_spec (:102-109), si_sdr / si_sdr_torch (:82-94), and the metrics of the calc_metrics step in batch form on the device:
-energy_ratios (:21-44), lsd (:16-19), snr_dB (:96-100); mean_std (:53-57) on the host."""
+energy_ratios (:21-44), lsd (:16-19), snr_dB (:96-100); mean_std (:53-57) on the host; stoi: STOI / ESTOI on the device under the
+signature of pystoi.stoi, which the reference's evaluation calls."""
+import warnings
+
 import numpy as np
 import torch
 
@@ -70,6 +73,32 @@ def lsd(s_hat, s, lengths=None, eps=1e-10):
     S_hat, S = ops.stft(s_hat, lengths=lengths), ops.stft(s, lengths=lengths)
     frames = None if lengths is None else [1 + int(v) // 128 for v in lengths]
     return ops.lsd_rows(S_hat, S, frames=frames, eps=eps)
+
+
+def stoi(x, y, fs_sig, extended=False, lengths=None):
+    """STOI (extended=False) or ESTOI (extended=True) of the processed signal y against the clean x at fs_sig Hz, under pystoi.stoi's
+    signature, on the device: resampling to 10 kHz and storm_stoi_rows (include/storm_hip.h has the definition; its numbers were checked
+    against a float64 restatement of the published algorithm, not against pystoi).  x, y: 1-D -> a float; [B, L] -> an fp64 tensor [B]
+    (lengths: per-row sample counts of a ragged batch).  numpy arrays are moved to the current HIP device; any other dtype (pystoi's callers
+    pass float64) is rounded to fp32, which is what the kernels read.  A signal with fewer than 30
+    frames left after the silent-frame gate gives 1e-5 and pystoi's RuntimeWarning."""
+    from .. import _lib, ops
+    dev = None
+    for v in (x, y):
+        if isinstance(v, torch.Tensor):
+            dev = v.device
+    if dev is None:
+        dev = torch.device("cpu") if _lib.is_sim() else torch.device("cuda", torch.cuda.current_device())
+    x, y = (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v)) for v in (x, y))
+    if x.shape != y.shape:
+        raise Exception("x and y should have the same length," + f"found {tuple(x.shape)} and {tuple(y.shape)}")      # (pystoi raises this)
+    one = x.dim() == 1
+    r, counts = ops.stoi_rows(_rows(x).to(dev, torch.float32), _rows(y).to(dev, torch.float32), lengths=lengths, fs=fs_sig, counts=True)
+    d = r[:, 1 if extended else 0]
+    if bool((counts[:, 2] < 1).any()):
+        warnings.warn("Not enough STFT frames to compute intermediate intelligibility measure after removing silent frames. Returning 1e-5. "
+                      "Please check you wav files", RuntimeWarning)
+    return float(d[0]) if one else d
 
 
 def mean_std(data):
