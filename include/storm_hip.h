@@ -438,7 +438,13 @@ int storm_rk_combine_rows_wide(double* out64, float* out32, const double* x, con
 int storm_rk_error_pair_rows(double* out, double* scratch, long long scratch_len, const double* xa, const double* xb,
                              const float* const* K, const double* coef_a, const double* coef_b, int n_terms, const double* h_rows,
                              double atol, double rtol, int B, long long n_complex_row, storm_stream_t s);
-/* fills z[B*n] complex with standard complex normal noise (Philox) */
+/* fills z[B*n] complex with standard complex normal noise (re, im ~ N(0, 1/2)).  Element i is Philox4x32-10 of
+ *   key     (k0, k1)         = (low, high 32 bits of seed)
+ *   counter (c0, c1, c2, c3) = (low, high 32 bits of i, low, high 32 bits of offset)
+ * followed by Box-Muller on the first two output words w0, w1: u = (float(w >> 8) + 0.5f) * 2^-24 in fp32, which lies in (0, 1]
+ * (the + 0.5f of 0xFFFFFF rounds to even), z = sqrtf(-logf(u1)) * (cos, sin)(fl32(2 pi) * u2).  Every entry point that takes
+ * (seed, offset) draws element i of row b from the same generator at i = b * n + i_in_row; the *_rs forms use key row_seeds[b]
+ * and i = i_in_row.  tests/philox_ref.py is an independent reference of this layout. */
 int storm_complex_randn(float* z, long long n_complex, uint64_t seed, uint64_t offset,
                         storm_stream_t s);
 /* rows form: z[B][n_per_row], row b = storm_complex_randn(n_per_row, row_seeds[b], offset) (see storm_ouve_prior_rs; the draw

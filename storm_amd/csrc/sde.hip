@@ -20,11 +20,14 @@ __device__ inline void philox4x32(uint64_t seed, uint64_t idx, uint64_t offset, 
 #pragma unroll
     for (int r = 0; r < 10; ++r) { philox_round(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
 }
-// standard complex normal: re, im ~ N(0, 1/2) independent (torch.randn_like on complex64)
+// standard complex normal: re, im ~ N(0, 1/2) independent (torch.randn_like on complex64).  Key = seed (words k0 low, k1 high),
+// counter words 0-1 = the element index (low, high), words 2-3 = the offset (low, high); Box-Muller on output words 0 and 1.
 __device__ inline float2 complex_normal(uint64_t seed, uint64_t idx, uint64_t offset) {
     uint32_t c[4];
     philox4x32(seed, idx, offset, c);
-    const float u1 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);     // (0,1)
+    // (0,1]: from 2^23 on `+ 0.5f` is a tie that rounds to even, so a top-24-bit value of 0xFFFFFF gives exactly 1.0 - r = 0 (both
+    // components +-0) and theta = fl32(2 pi) occur; the smallest value is 2^-25 (|z| = sqrt(25 ln 2), the largest magnitude)
+    const float u1 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
     const float u2 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
     const float r = sqrtf(-logf(u1));                                         // sqrt(-2 ln u / 2)
     float sn, cs;
