@@ -2,6 +2,7 @@
 """Score a directory of enhanced files against the clean and noisy ones - the reference's calc_metrics step on the device:
 
     python calc_metrics.py --clean_dir clean/ --noisy_dir noisy/ --enhanced_dir out/ [--batch 16] [--resample] [--stoi]
+                           [--align [--max-lag SECONDS]] [--hp-filter [HZ]]
 
 Files are matched by basename (every *.wav of --enhanced_dir needs its clean and noisy namesake).  Each triple is trimmed to its
 shortest member, the triples are bucketed by frame count and scored as ragged micro-batches (storm_amd.util.inference.score_batch:
@@ -15,7 +16,11 @@ SI-SDR / SI-SIR / SI-SAR, LSD and the input SNR, util/other.py:16-44, 96-100); P
 A file's line does not depend on --batch nor on the other files.  --resample: files of other rates are resampled to 16 kHz on the
 device when they are loaded (SpecsDataModule.resample); without it such a file is refused, as in enhancement.py.  --stoi: STOI and ESTOI
 of every file on the device, in the same micro-batches (storm_stoi_rows, defined in include/storm_hip.h and checked against a restatement
-of the published algorithm, not against pystoi); host pystoi is then not called, and a pesq column still appears when `pesq` imports."""
+of the published algorithm, not against pystoi); host pystoi is then not called, and a pesq column still appears when `pesq` imports.
+--hp-filter [HZ]: clean, noisy and enhanced file pass the reference's hp_filter first (Butterworth high-pass of order 10, 80 Hz unless given).
+--align: enhanced files that are a few samples off (a codec, a network that pads its input) are moved onto their clean file before any
+metric - the arg-max of the cross-correlation, searched within --max-lag seconds when given, zero-filled - and the column lag (last) says
+by how many samples at 16 kHz the file was late.  Host PESQ / ESTOI columns, where they appear, still read the files as loaded."""
 import glob
 import os
 from argparse import ArgumentParser
@@ -38,7 +43,13 @@ def main():
     p.add_argument("--batch", type=int, default=16, help="files per scoring micro-batch")
     p.add_argument("--resample", action="store_true", help="read files of any sample rate: each is resampled to 16 kHz on the device when it is loaded")
     p.add_argument("--stoi", action="store_true", help="append the columns stoi,estoi, computed on the device (pystoi is not needed and not called)")
+    p.add_argument("--align", action="store_true", help="move every enhanced file onto its clean file before scoring; appends the column lag (samples)")
+    p.add_argument("--max-lag", type=float, default=None, help="with --align: search delays of at most this many seconds (default: any)")
+    p.add_argument("--hp-filter", type=float, nargs="?", const=80.0, default=None, metavar="HZ",
+                   help="high-pass clean, noisy and enhanced at HZ (80 when no value is given) before scoring")
     args = p.parse_args()
+    if args.max_lag is not None and (not args.align or args.max_lag < 0):
+        p.error("--max-lag SECONDS (>= 0) goes with --align")
 
     from storm_amd import distributed as D
     from storm_amd.data_module import SpecsDataModule
@@ -59,7 +70,7 @@ def main():
         n = min(x.shape[0], y.shape[0], e.shape[0])
         triples.append((x[:n], y[:n], e[:n]))
     lengths = [t[0].shape[0] for t in triples]
-    device_columns = COLUMNS + (("stoi", "estoi") if args.stoi else ())
+    device_columns = COLUMNS + (("stoi", "estoi") if args.stoi else ()) + (("lag",) if args.align else ())
     values = {c: [None] * len(names) for c in device_columns}
     for ids in D.bucket_by_frames(lengths, args.batch):
         lens = [lengths[i] for i in ids]
@@ -68,6 +79,10 @@ def main():
             for j in range(3):
                 rows[j, k, :lens[k]] = triples[i][j]
         kw = dict(stoi=True, fs=SR) if args.stoi else {}
+        if args.align:
+            kw.update(align=True, max_lag=None if args.max_lag is None else int(round(args.max_lag * SR)))
+        if args.hp_filter is not None:
+            kw.update(hp=args.hp_filter, fs=SR)
         scores = {k: v.cpu() for k, v in score_batch(rows[0], rows[1], rows[2], lengths=lens, **kw).items()}
         for k, i in enumerate(ids):
             for c in device_columns:
@@ -83,8 +98,10 @@ def main():
         columns += ["pesq", "estoi"]
         values["pesq"] = [pesq(SR, x.cpu().numpy(), e.cpu().numpy(), "wb") for x, _, e in triples]
         values["estoi"] = [stoi(x.cpu().numpy(), e.cpu().numpy(), SR, extended=True) for x, _, e in triples]
+    if args.align:
+        columns += ["lag"]
 
-    table = [[f"{values[c][i]:.6f}" for c in columns] for i in range(len(names))]
+    table = [[f"{values[c][i]:.0f}" if c == "lag" else f"{values[c][i]:.6f}" for c in columns] for i in range(len(names))]
     with open(os.path.join(args.enhanced_dir, "_results.csv"), "w", encoding="utf-8") as f:
         f.write(",".join(["Filename", "Length"] + columns) + "\n")
         for i, name in enumerate(names):

@@ -601,6 +601,57 @@ int storm_crossfade_rows(const float* pool, int N, long long pool_stride, float*
                          const float* ramp, storm_stream_t st);
 
 /* ------------------------------------------------------------------------------------------
+ * Misaligned audio (the reference's util/other.py: align :153-157, hp_filter :76-80).  Every scoring entry point above assumes that its
+ * rows are sample-aligned; these find a delay, undo it and remove rumble without leaving the device.
+ *
+ * Delay search.  A row is ny samples of y and nr samples of ref (fp32).  The full cross-correlation at lag d is
+ *   c[d] = sum_n (double) y[n] * (double) ref[n + d],   n ascending from max(0, -d) to min(ny, nr - d) - 1,
+ *   d from max(-(ny - 1), -max_lag) to min(nr - 1, max_lag); max_lag < 0: unbounded (the reference's behaviour).
+ * A product of two fp32 values is exact in fp64, and c[d] is ONE fp64 chain in ascending n that starts at +0 (fused or unfused multiply-add:
+ * the same bits).  lag = the SMALLEST d at which c[d] is maximal (np.argmax's first index: an all-zero row gives the smallest d of the
+ * range), peak = c[lag].  The reference's align() rolls y by l = argmax(fftconvolve(ref, flip(y))) - (nr - 1): entry i of that convolution is
+ * c[i - (ny - 1)], so l = lag + ny - nr, which is lag for ny == nr.  Samples are expected finite.
+ *
+ * storm_xcorr_num_partials: scratch entries per row (STORM_XCORR_PARTIAL_BYTES each) for rows of Ny / Nr samples: the lag tiles of
+ *   STORM_XCORR_TILE consecutive lags (0: refused - a width < 1 or > 2^30).
+ * storm_xcorr_lag_rows: y fp32 [B][Ny], ref fp32 [B][Nr] (row strides in floats) -> lag int32 [B], peak fp64 [B].  y_len / ref_len (optional,
+ *   device int32 [B]): row b is its first y_len[b] / ref_len[b] samples, the rest is never read (a length < 1: lag 0, peak 0).  Two launches:
+ *   a workgroup owns one tile of lags and walks the tile's whole n range (no split over n, so no partial sums of a lag exist) and writes
+ *   the tile's (max, smallest lag) to scratch - the tiles with the longest overlaps are started first, and a thread keeps 8, 4 or 2
+ *   consecutive lags by the size of the launch (no bit depends on that choice); one thread per row then takes the
+ *   row's tiles in ascending order, replacing on strictly greater.  No atomics: a row's two outputs are the same bits alone, in any batch,
+ *   at any width, stride and position.  scratch: B * storm_xcorr_num_partials(Ny, Nr, max_lag) * STORM_XCORR_PARTIAL_BYTES bytes of device
+ *   memory, 8-byte aligned.
+ *
+ * storm_shift_rows: out[b][n] = x[b][(n - s) mod len] when wrap (np.roll(x, s) of the row's len samples), else x[b][n - s] where
+ *   0 <= n - s < len and 0 elsewhere; s = shift[b] is read from DEVICE memory (int32 [B], any value: a lag goes in as it came out);
+ *   samples from len up to N are written as zeros.  row_len optional as above.  Not in place.
+ *
+ * storm_sosfilt_rows: scipy.signal.sosfilt with zero initial state on every row.  sos: HOST fp64 [S][6] = (b0, b1, b2, a0 = 1, a1, a2) per
+ *   section, 1 <= S <= STORM_SOS_MAX_SECTIONS.  Per sample n, for each section s in order, xc starting as (double) x[n]:
+ *     xn = b0 xc + z0;   z0 = b1 xc - a1 xn + z1;   z1 = b2 xc - a2 xn;   xc = xn
+ *   evaluated in exactly that order in fp64, every multiply and add rounded separately (never contracted), subnormals kept.  out: fp64
+ *   [B][L], or fp32 (that value rounded once) when out_f32; row strides in elements of their own type; samples from row_len[b] up to L are
+ *   written as zeros.  Rows are independent; the sections of a row overlap as a pipeline across lanes, which changes no bit.
+ * storm_butter_sos (host, no device): the sections of scipy.signal.butter(order, wn, 'hp' | 'lp', output='sos') for an EVEN order, in closed
+ *   form in fp64 into the CALLER's order / 2 * 6 doubles: the prototype's poles -exp(j pi m / (2 order)), pre-warped with 4 tan(pi wn / 2),
+ *   lp2hp (highpass != 0) or lp2lp, the bilinear transform at fs = 2, conjugate poles paired, the pair nearest the unit circle last, the
+ *   whole gain in the first section's numerator g [1, -2, 1] (low-pass: g [1, 2, 1]).  Agrees with scipy to a few units in the last place
+ *   (another libm's tan / cos).  Refused: an odd order, order outside [2, 2 STORM_SOS_MAX_SECTIONS], wn outside (0, 1). */
+#define STORM_XCORR_TILE 512
+#define STORM_XCORR_PARTIAL_BYTES 16
+#define STORM_SOS_MAX_SECTIONS 16
+int storm_xcorr_num_partials(long long Ny, long long Nr, int max_lag);
+int storm_xcorr_lag_rows(const float* y, const float* ref, int* lag, double* peak, void* scratch, long long scratch_bytes, int B,
+                         long long Ny, long long Nr, long long stride_y, long long stride_ref, const int* y_len, const int* ref_len,
+                         int max_lag, storm_stream_t st);
+int storm_shift_rows(const float* x, float* out, const int* shift, int B, long long N, long long stride_x, long long stride_out,
+                     const int* row_len, int wrap, storm_stream_t st);
+int storm_sosfilt_rows(const float* x, void* out, const double* sos, int S, int B, long long L, long long stride_x, long long stride_out,
+                       const int* row_len, int out_f32, storm_stream_t st);
+int storm_butter_sos(int order, double wn, int highpass, double* sos_out);
+
+/* ------------------------------------------------------------------------------------------
  * ConvTasNet (backbones/convtasnet.py): the time-domain denoiser.  Activations are channels-last [B][L][C] in `dtype`
  * (C % 8 == 0); the TCN's running sums `output` / `skip_connection` are fp32 [B][L][BN]; statistics are fp32.  A global layer
  * norm (GroupNorm(1, C, eps) over all of C x L of a row) is never materialised: the producing kernel writes per-wave

@@ -23,6 +23,9 @@ ABI_VERSION = 2                  # include/storm_hip.h: STORM_ABI_VERSION
 METRICS_CHUNK = 16384            # include/storm_hip.h: STORM_METRICS_CHUNK, the samples one workgroup of storm_energy_ratios_rows sums
 RESAMPLE_TILE = 1024             # include/storm_hip.h: STORM_RESAMPLE_TILE, the outputs one workgroup of storm_resample_poly computes
 CROSSFADE_TILE = 1024            # include/storm_hip.h: STORM_CROSSFADE_TILE, the outputs one workgroup of storm_crossfade_rows computes
+XCORR_TILE = 512                 # include/storm_hip.h: STORM_XCORR_TILE, the consecutive lags one workgroup of storm_xcorr_lag_rows owns
+XCORR_PARTIAL_BYTES = 16         # include/storm_hip.h: STORM_XCORR_PARTIAL_BYTES
+SOS_MAX_SECTIONS = 16            # include/storm_hip.h: STORM_SOS_MAX_SECTIONS
 RAMP_KINDS = {"hann": 0, "linear": 1}        # include/storm_hip.h: STORM_RAMP_HANN, STORM_RAMP_LINEAR
 
 
@@ -159,6 +162,11 @@ _SIGNATURES = {
     "storm_stoi_rows": ([_vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _vp, _vp], C.c_int),
     "storm_crossfade_ramp": ([_i, _i, _vp], C.c_int),
     "storm_crossfade_rows": ([_vp, _i, _ll, _vp, _i, _ll, _ll, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp], C.c_int),
+    "storm_xcorr_num_partials": ([_ll, _ll, _i], C.c_int),
+    "storm_xcorr_lag_rows": ([_vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _ll, _vp, _vp, _i, _vp], C.c_int),
+    "storm_shift_rows": ([_vp, _vp, _vp, _i, _ll, _ll, _ll, _vp, _i, _vp], C.c_int),
+    "storm_sosfilt_rows": ([_vp, _vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _i, _vp], C.c_int),
+    "storm_butter_sos": ([_i, C.c_double, _i, _vp], C.c_int),
     "storm_tasnet_num_partials":([_i, _i, _i], C.c_int),
     "storm_tasnet_frames": ([_ll, _i], C.c_int),
     "storm_tasnet_encode": ([_vp, _ll, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp], C.c_int),

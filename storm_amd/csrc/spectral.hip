@@ -347,3 +347,6 @@ extern "C" int storm_resample_poly(const float* x, float* y, const float* taps, 
 
 // ---- long recordings (storm_crossfade_rows, storm_crossfade_ramp): the stitch of enhanced windows, kernel and entry points ----
 #include "longform.h"
+
+// ---- misaligned audio (storm_xcorr_lag_rows, storm_shift_rows, storm_sosfilt_rows, storm_butter_sos): delay search, shift, biquad cascade ----
+#include "align.h"

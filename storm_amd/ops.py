@@ -1035,6 +1035,96 @@ def stoi_rows(clean, estimate, lengths=None, fs=16000, counts=False):
     return (out, ws[:4 * B].reshape(B, 4)[:, :3].clone()) if counts else out
 
 
+# ---------------------------------------------------------------- misaligned audio --------
+XCORR_TILE = L.XCORR_TILE                # consecutive lags per workgroup of storm_xcorr_lag_rows (tests place delays around its multiples)
+SOS_MAX_SECTIONS = L.SOS_MAX_SECTIONS
+
+
+def _wave_rows(who, name, x):
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{who}: {name} is {x.dtype} {tuple(x.shape)}, expected a float32 batch [B, L]")
+    return x if x.stride(1) == 1 else x.contiguous()
+
+
+def xcorr_lag_rows(y, ref, lengths=None, ref_lengths=None, max_lag=None):
+    """(lag int32 [B], peak fp64 [B]) per row of two fp32 waveform batches y [B, Ny] and ref [B, Nr] (rows may be strided views): the
+    smallest lag d at which the full cross-correlation c[d] = sum_n y[n] ref[n + d] is largest, and that value (include/storm_hip.h:
+    storm_xcorr_lag_rows; every c[d] is one fp64 chain in ascending n).  ref is y delayed by `lag` samples.  lengths / ref_lengths:
+    per-row sample counts of a ragged batch (the rest of a row is not read).  max_lag: only |d| <= max_lag is searched (None: every
+    lag).  Two launches, no synchronisation; a row's outputs do not depend on the batch it is in."""
+    y, ref = _wave_rows("xcorr_lag_rows", "y", y), _wave_rows("xcorr_lag_rows", "ref", ref)
+    B, Ny = y.shape
+    Nr = ref.shape[1]
+    if ref.shape[0] != B:
+        raise ValueError(f"xcorr_lag_rows: {tuple(y.shape)} against {tuple(ref.shape)}")
+    _metric_lengths("xcorr_lag_rows", lengths, B, Ny, "lengths")
+    _metric_lengths("xcorr_lag_rows", ref_lengths, B, Nr, "ref_lengths")
+    ml = -1 if max_lag is None else int(max_lag)
+    if ml < -1 or ml > 2 ** 30:
+        raise ValueError(f"xcorr_lag_rows: max_lag={max_lag} (None or a sample count >= 0)")
+    tiles = L.lib().storm_xcorr_num_partials(Ny, Nr, ml)
+    if tiles < 1:
+        raise ValueError(f"xcorr_lag_rows: rows of {Ny} / {Nr} samples")
+    lag, peak = _alloc((B,), torch.int32, y), _alloc((B,), torch.float64, y)
+    ws = torch.empty((B * tiles * L.XCORR_PARTIAL_BYTES // 8,), dtype=torch.float64, device=y.device)
+    sy, sr = (y.stride(0), ref.stride(0)) if B > 1 else (Ny, Nr)   # (a one-row tensor's row stride is whatever its producer left there)
+    yl, rl = _row_len(lengths, y), _row_len(ref_lengths, y)
+    L.check(L.lib().storm_xcorr_lag_rows(L.ptr_rows(y), L.ptr_rows(ref), L.ptr(lag), L.ptr(peak), L.ptr(ws), 8 * ws.numel(), B, Ny, Nr, sy, sr,
+                                         L.ptr(yl), L.ptr(rl), ml, L.stream()), "storm_xcorr_lag_rows")
+    return lag, peak
+
+
+def shift_rows(x, shift, lengths=None, wrap=True):
+    """x fp32 [B, N] moved by a per-row shift that stays on the device: out[b, n] = x[b, (n - s) mod len] (wrap=True: np.roll(row, s)) or
+    x[b, n - s] inside the row and 0 outside (wrap=False); s = shift[b], an int32 DEVICE tensor [B] (a list or int is uploaded).  lengths:
+    per-row sample counts; samples past them are written as zeros.  One launch (storm_shift_rows)."""
+    x = _wave_rows("shift_rows", "x", x)
+    B, N = x.shape
+    if isinstance(shift, torch.Tensor):
+        shift = shift.to(device=x.device, dtype=torch.int32).reshape(-1).contiguous()
+    else:
+        shift = torch.tensor([int(shift)] * B if isinstance(shift, int) else [int(v) for v in shift], dtype=torch.int32, device=x.device)
+    if shift.numel() != B:
+        raise ValueError(f"shift_rows: {shift.numel()} shifts for a batch of {B} rows")
+    _metric_lengths("shift_rows", lengths, B, N, "lengths")
+    out = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    rl = _row_len(lengths, x)
+    L.check(L.lib().storm_shift_rows(L.ptr_rows(x), L.ptr(out), L.ptr(shift), B, N, x.stride(0) if B > 1 else N, out.stride(0),
+                                     L.ptr(rl), int(bool(wrap)), L.stream()), "storm_shift_rows")
+    return out
+
+
+def butter_sos(order, wn, btype="hp"):
+    """The second-order sections of scipy.signal.butter(order, wn, btype, output='sos') for an even order: a float64 CPU tensor [order / 2, 6],
+    designed by the library in closed form (storm_butter_sos).  wn: the cut-off as a fraction of the Nyquist rate; btype 'hp' or 'lp'."""
+    kinds = {"hp": 1, "highpass": 1, "high": 1, "lp": 0, "lowpass": 0, "low": 0}
+    if btype not in kinds:
+        raise ValueError(f"butter_sos: btype {btype!r} ('hp' or 'lp')")
+    order = int(order)
+    sos = torch.zeros((max(order // 2, 1), 6), dtype=torch.float64)
+    L.check(L.lib().storm_butter_sos(order, float(wn), kinds[btype], sos.data_ptr()), "storm_butter_sos")
+    return sos
+
+
+def sosfilt_rows(x, sos, lengths=None, out_dtype=torch.float64):
+    """scipy.signal.sosfilt(sos, row) with zero initial state for every row of x fp32 [B, L]: out_dtype float64 [B, L], or float32 = that value
+    rounded once.  sos: [S, 6] (a tensor or array; read on the host as float64, a0 = 1).  lengths: per-row sample counts; the tail of a row is
+    zero.  One launch (storm_sosfilt_rows): every multiply and add of the recurrence is rounded separately, in scipy's order."""
+    x = _wave_rows("sosfilt_rows", "x", x)
+    B, Lw = x.shape
+    if out_dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"sosfilt_rows: out_dtype {out_dtype} (float64 or float32)")
+    sos = torch.as_tensor(sos).detach().to("cpu", torch.float64).contiguous()
+    if sos.dim() != 2 or sos.shape[1] != 6 or not 1 <= sos.shape[0] <= SOS_MAX_SECTIONS:
+        raise ValueError(f"sosfilt_rows: sos {tuple(sos.shape)}, expected [S, 6] with 1 <= S <= {SOS_MAX_SECTIONS}")
+    _metric_lengths("sosfilt_rows", lengths, B, Lw, "lengths")
+    out = torch.empty((B, Lw), dtype=out_dtype, device=x.device)
+    rl = _row_len(lengths, x)
+    L.check(L.lib().storm_sosfilt_rows(L.ptr_rows(x), L.ptr(out), sos.data_ptr(), sos.shape[0], B, Lw, x.stride(0) if B > 1 else Lw, out.stride(0),
+                                       L.ptr(rl), int(out_dtype == torch.float32), L.stream()), "storm_sosfilt_rows")
+    return out
+
+
 # ---------------------------------------------------------------- ConvTasNet --------------
 TASNET_ENCODE, TASNET_POINTWISE, TASNET_DEPTHWISE = 0, 1, 2
 

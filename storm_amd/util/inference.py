@@ -34,19 +34,33 @@ def _optional(name, attr):
 METRIC_KEYS = ("si_sdr", "si_sir", "si_sar", "lsd", "isnr")
 
 
-def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000):
+def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, align=False, max_lag=None, hp=None):
     """The calc_metrics numbers of one micro-batch of device waveforms [B, L]: a dict of fp64 [B] tensors si_sdr / si_sir / si_sar
     (energy_ratios(estimate, clean, noisy - clean), util/other.py:35-44), lsd (estimate against clean, :16-19) and isnr (snr_dB(clean,
     noisy - clean), :96-100).  lengths: per-row sample counts of a ragged batch.  One energy launch pair, two STFTs and one LSD launch
     pair; every row's numbers are those of its own one-row call.  stoi=True adds the keys stoi and estoi: ops.stoi_rows(clean, estimate)
-    of waveforms at `fs` Hz (resampled to 10 kHz on the device; include/storm_hip.h has the definition)."""
+    of waveforms at `fs` Hz (resampled to 10 kHz on the device; include/storm_hip.h has the definition).
+    hp=HZ: clean, noisy and estimate first pass the reference's hp_filter (order 10 at HZ for waveforms at `fs`; ops.sosfilt_rows, rounded
+    to fp32 once).  align=True: the estimate is then moved onto the clean row by the arg-max of their cross-correlation
+    (ops.xcorr_lag_rows, |lag| <= max_lag samples when given) and ZERO-FILLED, not rolled - rolled-in samples are unrelated audio that would
+    enter every energy - before any metric; the result gains the key lag (int32 [B]): the samples by which the estimate was late.
+    Without the three keywords nothing changes."""
     from .. import ops
     clean, noisy, estimate = clean.float(), noisy.float(), estimate.float()
+    if hp is not None:
+        sos = ops.butter_sos(10, float(hp) / fs * 2, "hp")
+        clean, noisy, estimate = (ops.sosfilt_rows(v, sos, lengths=lengths, out_dtype=torch.float32) for v in (clean, noisy, estimate))
+    lag = None
+    if align:
+        back, _ = ops.xcorr_lag_rows(estimate, clean, lengths=lengths, ref_lengths=lengths, max_lag=max_lag)
+        estimate, lag = ops.shift_rows(estimate, back, lengths=lengths, wrap=False), -back
     r = ops.energy_ratios_rows(estimate, clean, noisy - clean, lengths=lengths)
     out = {"si_sdr": r[:, 0], "si_sir": r[:, 1], "si_sar": r[:, 2], "lsd": lsd(estimate, clean, lengths=lengths), "isnr": r[:, 3]}
     if stoi:
         d = ops.stoi_rows(clean, estimate, lengths=lengths, fs=fs)
         out["stoi"], out["estoi"] = d[:, 0], d[:, 1]
+    if lag is not None:
+        out["lag"] = lag
     return out
 
 

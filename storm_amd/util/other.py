@@ -1,7 +1,7 @@
 """Small utilities of sgmse/util/other.py that the hot path and the evaluation loop use:
 pad_spec (:102-109), si_sdr / si_sdr_torch (:82-94), and the metrics of the calc_metrics step in batch form on the device:
 energy_ratios (:21-44), lsd (:16-19), snr_dB (:96-100); mean_std (:53-57) on the host; stoi: STOI / ESTOI on the device under the
-signature of pystoi.stoi, which the reference's evaluation calls."""
+signature of pystoi.stoi, which the reference's evaluation calls; align (:153-157) and hp_filter (:76-80) on the device."""
 import warnings
 
 import numpy as np
@@ -99,6 +99,46 @@ def stoi(x, y, fs_sig, extended=False, lengths=None):
         warnings.warn("Not enough STFT frames to compute intermediate intelligibility measure after removing silent frames. Returning 1e-5. "
                       "Please check you wav files", RuntimeWarning)
     return float(d[0]) if one else d
+
+
+def _device_rows(*xs):
+    """the arguments as tensors on one device (numpy arrays are moved to the current HIP device), and whether the first is 1-D"""
+    from .. import _lib
+    dev = None
+    for v in xs:
+        if isinstance(v, torch.Tensor):
+            dev = v.device
+    if dev is None:
+        dev = torch.device("cpu") if _lib.is_sim() else torch.device("cuda", torch.cuda.current_device())
+    ts = [v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v)) for v in xs]
+    return [_rows(t.to(dev)) for t in ts], ts[0].dim() == 1
+
+
+def align(y, ref, lengths=None, max_lag=None, wrap=True):
+    """y moved onto ref (util/other.py:153-157) on the device: the arg-max of the full cross-correlation of every row (storm_xcorr_lag_rows:
+    two launches, exact fp64 chains instead of the reference's fftconvolve - the two agree wherever the peak is clear), then one gather
+    (storm_shift_rows) that reads the lag from device memory.  Nothing is synchronised and the result stays on the device.  y, ref: 1-D or
+    [B, L] (fp32 is what the kernels read); lengths: per-row sample counts of a ragged batch, for y and ref alike.  max_lag: search only
+    |lag| <= max_lag samples (None: unbounded, as the reference).  wrap=True rolls like the reference's np.roll; wrap=False fills with zeros.
+    The shift is the reference's expression l = argmax - (len(ref) - 1) taken literally, which is lag + len(y) - len(ref): the lag itself for
+    equal lengths; for unequal lengths that is the reference's own (surprising) choice, reproduced here, and costs one more tiny launch."""
+    from .. import ops
+    (yr, rr), one = _device_rows(y, ref)
+    lag, _ = ops.xcorr_lag_rows(yr, rr, lengths=lengths, ref_lengths=lengths, max_lag=max_lag)
+    if lengths is None and yr.shape[1] != rr.shape[1]:
+        lag = lag + (yr.shape[1] - rr.shape[1])
+    out = ops.shift_rows(yr, lag, lengths=lengths, wrap=wrap)
+    return out[0] if one else out
+
+
+def hp_filter(signal, cut_off=80, order=10, sr=16000, lengths=None):
+    """Butterworth high-pass of every row (util/other.py:76-80): the sections of scipy.signal.butter(order, cut_off / sr * 2, 'hp',
+    output='sos') as the library designs them (storm_butter_sos: even orders) through storm_sosfilt_rows, which restates scipy.signal.sosfilt
+    bit for bit.  signal: [L] or [B, L] (fp32 is what the kernel reads); returns float64 like the reference, on the device."""
+    from .. import ops
+    (x,), one = _device_rows(signal)
+    out = ops.sosfilt_rows(x, ops.butter_sos(order, cut_off / sr * 2, "hp"), lengths=lengths, out_dtype=torch.float64)
+    return out[0] if one else out
 
 
 def mean_std(data):
