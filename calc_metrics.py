@@ -2,7 +2,7 @@
 """Score a directory of enhanced files against the clean and noisy ones - the reference's calc_metrics step on the device:
 
     python calc_metrics.py --clean_dir clean/ --noisy_dir noisy/ --enhanced_dir out/ [--batch 16] [--resample] [--stoi]
-                           [--align [--max-lag SECONDS]] [--hp-filter [HZ]]
+                           [--align [--max-lag SECONDS]] [--hp-filter [HZ]] [--sdr [TAPS]]
 
 Files are matched by basename (every *.wav of --enhanced_dir needs its clean and noisy namesake).  Each triple is trimmed to its
 shortest member, the triples are bucketed by frame count and scored as ragged micro-batches (storm_amd.util.inference.score_batch:
@@ -10,7 +10,7 @@ SI-SDR / SI-SIR / SI-SAR, LSD and the input SNR, util/other.py:16-44, 96-100); P
 / `pystoi` packages import.  Written into --enhanced_dir:
 
     _results.csv       Filename,Length,iSNR,si_sdr,si_sir,si_sar,lsd[,pesq,estoi] - one line per file, Length in samples at 16 kHz
-                       (--stoi: ...,lsd[,pesq],stoi,estoi)
+                       (--stoi: ...,lsd[,pesq],stoi,estoi; --sdr: then sdr; --align: lag, always last)
     _avg_results.txt   metric: mean ± std of each column (mean_std, NaNs dropped)
 
 A file's line does not depend on --batch nor on the other files.  --resample: files of other rates are resampled to 16 kHz on the
@@ -20,7 +20,11 @@ of the published algorithm, not against pystoi); host pystoi is then not called,
 --hp-filter [HZ]: clean, noisy and enhanced file pass the reference's hp_filter first (Butterworth high-pass of order 10, 80 Hz unless given).
 --align: enhanced files that are a few samples off (a codec, a network that pads its input) are moved onto their clean file before any
 metric - the arg-max of the cross-correlation, searched within --max-lag seconds when given, zero-filled - and the column lag (last) says
-by how many samples at 16 kHz the file was late.  Host PESQ / ESTOI columns, where they appear, still read the files as loaded."""
+by how many samples at 16 kHz the file was late.  Host PESQ / ESTOI columns, where they appear, still read the files as loaded.
+--sdr [TAPS]: the column sdr, the BSS-eval SDR that allows the enhanced file a linear filter of TAPS taps of the clean one (512 unless
+given, at most 512) where si_sdr allows a gain: a codec's or a resampler's colouring and a delay below TAPS samples are not booked as
+distortion (storm_bss_sdr_rows, defined in include/storm_hip.h; not compared with mir_eval).  It is computed on what --hp-filter and
+--align leave; a file that is exactly a filtered clean file prints inf."""
 import glob
 import os
 from argparse import ArgumentParser
@@ -47,7 +51,11 @@ def main():
     p.add_argument("--max-lag", type=float, default=None, help="with --align: search delays of at most this many seconds (default: any)")
     p.add_argument("--hp-filter", type=float, nargs="?", const=80.0, default=None, metavar="HZ",
                    help="high-pass clean, noisy and enhanced at HZ (80 when no value is given) before scoring")
+    p.add_argument("--sdr", type=int, nargs="?", const=512, default=None, metavar="TAPS",
+                   help="append the column sdr: the BSS-eval SDR with a filter of TAPS taps (512 when no value is given), on the device")
     args = p.parse_args()
+    if args.sdr is not None and not 1 <= args.sdr <= 512:
+        p.error("--sdr TAPS: 1 to 512")
     if args.max_lag is not None and (not args.align or args.max_lag < 0):
         p.error("--max-lag SECONDS (>= 0) goes with --align")
 
@@ -70,7 +78,7 @@ def main():
         n = min(x.shape[0], y.shape[0], e.shape[0])
         triples.append((x[:n], y[:n], e[:n]))
     lengths = [t[0].shape[0] for t in triples]
-    device_columns = COLUMNS + (("stoi", "estoi") if args.stoi else ()) + (("lag",) if args.align else ())
+    device_columns = COLUMNS + (("stoi", "estoi") if args.stoi else ()) + (("sdr",) if args.sdr is not None else ()) + (("lag",) if args.align else ())
     values = {c: [None] * len(names) for c in device_columns}
     for ids in D.bucket_by_frames(lengths, args.batch):
         lens = [lengths[i] for i in ids]
@@ -83,6 +91,8 @@ def main():
             kw.update(align=True, max_lag=None if args.max_lag is None else int(round(args.max_lag * SR)))
         if args.hp_filter is not None:
             kw.update(hp=args.hp_filter, fs=SR)
+        if args.sdr is not None:
+            kw.update(sdr=True, sdr_taps=args.sdr)
         scores = {k: v.cpu() for k, v in score_batch(rows[0], rows[1], rows[2], lengths=lens, **kw).items()}
         for k, i in enumerate(ids):
             for c in device_columns:
@@ -98,6 +108,8 @@ def main():
         columns += ["pesq", "estoi"]
         values["pesq"] = [pesq(SR, x.cpu().numpy(), e.cpu().numpy(), "wb") for x, _, e in triples]
         values["estoi"] = [stoi(x.cpu().numpy(), e.cpu().numpy(), SR, extended=True) for x, _, e in triples]
+    if args.sdr is not None:
+        columns += ["sdr"]
     if args.align:
         columns += ["lag"]
 

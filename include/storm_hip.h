@@ -652,6 +652,65 @@ int storm_sosfilt_rows(const float* x, void* out, const double* sos, int S, int 
 int storm_butter_sos(int order, double wn, int highpass, double* sos_out);
 
 /* ------------------------------------------------------------------------------------------
+ * BSS-eval SDR: the signal-to-distortion ratio that allows the estimate a short linear FILTER of the reference (Vincent, Gribonval,
+ * Fevotte 2006; what mir_eval.separation.bss_eval_sources and fast_bss_eval call SDR), where SI-SDR allows a gain and the alignment above a
+ * gain and one integer delay.  The reference project does not compute it, so this comment is the specification.
+ *
+ * Per row: reference s[0..L), estimate e[0..L), both fp32; filter length F = flen, 1 <= F <= STORM_BSS_MAX_TAPS.
+ *
+ * Correlations.
+ *   G[k] = sum_n (double) s[n] * (double) s[n + k],   k = 0 .. F - 1,   n = 0 .. L - 1 - k   (an empty sum is 0)
+ *   D[k] = sum_n (double) s[n] * (double) e[n + k]
+ *   Ee   = sum_n (double) e[n]^2
+ * A product of two fp32 values is exact in fp64.  The order of summation is fixed by the sample index alone: n is cut into pieces of
+ * STORM_BSS_PIECE samples (the cut of storm_energy_ratios_rows); a term belongs to the piece of the index of its FIRST factor s[n] (of
+ * e[n] for Ee) - s[n + k] / e[n + k] may lie in the next piece; inside a piece every G[k], D[k] and Ee is ONE fp64 chain in ascending n
+ * that starts at +0 (fused or unfused multiply-add: the same bits); the pieces are then added in ascending order from +0.  No atomics:
+ * these 2 F + 1 numbers are the same bits for a row alone, in any batch, at any width, stride and position, and np.cumsum per lag and
+ * piece reproduces them bit for bit.
+ *
+ * Filter.  C solves Toeplitz(G) C = D by the Levinson-Durbin recursion in fp64 (Golub & Van Loan alg. 4.7.3, the algorithm behind
+ * scipy.linalg.solve_toeplitz):
+ *   a = [1], E = G[0], C[0] = D[0] / E
+ *   for m = 1 .. F - 1:
+ *       lam = -(sum_{i<m} a[i] G[m - i]) / E
+ *       a[i] <- a[i] + lam a[m - i]      (i = 0 .. m, a[m] = 0 before)
+ *       E <- E (1 - lam^2)
+ *       mu = (D[m] - sum_{i<m} C[i] G[m - i]) / E
+ *       C[i] <- C[i] + mu a[m - i]       (i = 0 .. m, the new a)
+ * Every multiply-add is a fused one.  The two dot products of order m are summed in a shape that depends on m only: entry i belongs to
+ * lane i mod 64 of one wave, a lane adds its entries i < m as one fma chain in ascending i from +0, and the 64 lane sums are added by the
+ * xor butterfly 32, 16, 8, 4, 2, 1.  Fixed, so rows stay batch-independent; NOT pinned to numpy bit for bit.
+ *
+ * Result.  P = sum_k D[k] C[k] (the same shape) and sdr = 10 log10(P / (Ee - P)): the energy of the projection of the zero-padded estimate
+ * onto the span of the F delayed copies of the reference over the energy of what is left of it (||e - proj||^2 = Ee - P: the projection is
+ * orthogonal).  This is mir_eval.separation.bss_eval_sources(s[None], e[None])[0] with exact linear correlations; mir_eval takes its
+ * correlations from an FFT of length 2^ceil(log2(L + 512)), which wraps for some L - its artefact, not part of this definition.  F = 1 is
+ * SI-SDR without its eps.  argmax |C| is the delay the alignment above would find.
+ *
+ * Edge rules.  Ee - P <= 0: +inf.  Trust range: at an SDR of x dB the difference Ee - P carries a relative error of about
+ * 10^(x / 10) * 1e-15, so the number means something up to roughly 100 dB (an exactly filtered row measured Ee - P = -1e-10 at
+ * Ee = 5.5e4).  P <= 0 with Ee - P > 0: -inf.  NaN: a row of fewer than 1 sample, G[0] == 0, Ee == 0, or an E that is <= 0 or not finite
+ * at some order - a reference whose F delays are numerically dependent; mir_eval falls back to a least-squares solve there, this refuses
+ * by NaN.  No diagonal loading is applied (band-limited references down to min E / G[0] = 5e-5 solve to the same SDR as a dense solver).
+ * The filter of a NaN row is NaN; the correlations of a row of fewer than 1 sample are zeros.  Samples are expected finite.
+ * Out of scope: SIR / SAR against a noise reference (a block-Toeplitz system of twice the size, not a Levinson problem), a time-varying
+ * filter, permutations of several sources.
+ *
+ * storm_bss_sdr_scratch_bytes: device scratch for rows of L samples: B * ceil(L / STORM_BSS_PIECE) * (2 flen + 1) doubles (0: refused -
+ *   B outside 1 .. 65535, L outside 1 .. 2^30, flen outside 1 .. STORM_BSS_MAX_TAPS).
+ * storm_bss_sdr_rows: ref, est fp32 [B][L] (row strides in floats) -> sdr fp64 [B]; filt (optional) fp64 [B][flen] = C; parts (optional)
+ *   fp64 [B][2 flen + 1] = G, D, Ee.  row_len (optional, device int32 [B]): row b is its first row_len[b] samples, the rest is never read.
+ *   Two launches: a workgroup per (row, piece) computes the piece's 2 flen + 1 chains together - a thread keeps 8, 4 or 2 consecutive lags
+ *   of both banks by the size of the launch (no bit depends on that choice) - and writes them to scratch; one wave per row then adds the
+ *   pieces, runs the recursion and forms the number.  scratch: 8-byte aligned device memory of at least the query's answer. */
+#define STORM_BSS_MAX_TAPS 512
+#define STORM_BSS_PIECE 16384
+long long storm_bss_sdr_scratch_bytes(int B, long long L, int flen);
+int storm_bss_sdr_rows(const float* ref, const float* est, double* sdr, double* filt, double* parts, void* scratch, long long scratch_bytes,
+                       int B, long long L, long long stride_ref, long long stride_est, const int* row_len, int flen, storm_stream_t st);
+
+/* ------------------------------------------------------------------------------------------
  * ConvTasNet (backbones/convtasnet.py): the time-domain denoiser.  Activations are channels-last [B][L][C] in `dtype`
  * (C % 8 == 0); the TCN's running sums `output` / `skip_connection` are fp32 [B][L][BN]; statistics are fp32.  A global layer
  * norm (GroupNorm(1, C, eps) over all of C x L of a row) is never materialised: the producing kernel writes per-wave

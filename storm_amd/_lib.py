@@ -26,6 +26,8 @@ CROSSFADE_TILE = 1024            # include/storm_hip.h: STORM_CROSSFADE_TILE, th
 XCORR_TILE = 512                 # include/storm_hip.h: STORM_XCORR_TILE, the consecutive lags one workgroup of storm_xcorr_lag_rows owns
 XCORR_PARTIAL_BYTES = 16         # include/storm_hip.h: STORM_XCORR_PARTIAL_BYTES
 SOS_MAX_SECTIONS = 16            # include/storm_hip.h: STORM_SOS_MAX_SECTIONS
+BSS_MAX_TAPS = 512               # include/storm_hip.h: STORM_BSS_MAX_TAPS, the longest filter storm_bss_sdr_rows allows the estimate
+BSS_PIECE = 16384                # include/storm_hip.h: STORM_BSS_PIECE, the samples one workgroup of storm_bss_sdr_rows correlates
 RAMP_KINDS = {"hann": 0, "linear": 1}        # include/storm_hip.h: STORM_RAMP_HANN, STORM_RAMP_LINEAR
 
 
@@ -167,6 +169,8 @@ _SIGNATURES = {
     "storm_shift_rows": ([_vp, _vp, _vp, _i, _ll, _ll, _ll, _vp, _i, _vp], C.c_int),
     "storm_sosfilt_rows": ([_vp, _vp, _vp, _i, _i, _ll, _ll, _ll, _vp, _i, _vp], C.c_int),
     "storm_butter_sos": ([_i, C.c_double, _i, _vp], C.c_int),
+    "storm_bss_sdr_scratch_bytes": ([_i, _ll, _i], C.c_longlong),
+    "storm_bss_sdr_rows": ([_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _vp, _i, _vp], C.c_int),
     "storm_tasnet_num_partials":([_i, _i, _i], C.c_int),
     "storm_tasnet_frames": ([_ll, _i], C.c_int),
     "storm_tasnet_encode": ([_vp, _ll, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp], C.c_int),

@@ -44,6 +44,7 @@ struct Switches {
                                 //   ladder of choose_variant without the batch-ranged table, no small-call K split, no key-range split of the attention - an utterance then
                                 //   comes out the same bits alone and in any batch (serving with dynamic batching; costs the batch-aware selections)
     int xcorr_lags = 0;         // STORM_XCORR_LAGS: lags per thread of the delay search - 0 = the launcher's rule (by the launch's lag count), 2 / 4 / 8 = that many (tests, A/B; no bit depends on it)
+    int bss_lags = 0;           // STORM_BSS_LAGS: lags per thread of the BSS-eval correlations - 0 = the launcher's rule (by the launch's chain count), 2 / 4 / 8 = that many (tests, A/B; no bit depends on it)
     int graph = -1;             // STORM_GRAPH: HIP-graph replay of storm_ncsnpp_forward - -1 = the handle's mode (storm_ncsnpp_set_graph), 0 = never, 1 = always (A/B)
     unsigned long long conv_trace_ptr = 0;   // STORM_CONV_TRACE_PTR (profiling build): device buffer of tools/conv_trace.py
 };

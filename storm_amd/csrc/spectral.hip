@@ -350,3 +350,6 @@ extern "C" int storm_resample_poly(const float* x, float* y, const float* taps, 
 
 // ---- misaligned audio (storm_xcorr_lag_rows, storm_shift_rows, storm_sosfilt_rows, storm_butter_sos): delay search, shift, biquad cascade ----
 #include "align.h"
+
+// ---- BSS-eval SDR (storm_bss_sdr_rows, storm_bss_sdr_scratch_bytes): lag correlations per piece, Levinson-Durbin solve per row ----
+#include "bss.h"

@@ -1125,6 +1125,39 @@ def sosfilt_rows(x, sos, lengths=None, out_dtype=torch.float64):
     return out
 
 
+# ---------------------------------------------------------------- BSS-eval SDR ------------
+BSS_MAX_TAPS = L.BSS_MAX_TAPS            # the longest filter storm_bss_sdr_rows allows the estimate
+BSS_PIECE = L.BSS_PIECE                  # samples per workgroup of its correlations (tests place lengths around it)
+
+
+def bss_sdr_rows(reference, estimate, lengths=None, flen=512, return_filter=False, return_parts=False):
+    """fp64 [B]: the BSS-eval SDR in dB per row of two fp32 waveform batches [B, L] (rows may be strided views) - the estimate projected onto
+    the span of `flen` delayed copies of the reference, the energy of the projection over the energy of the rest (include/storm_hip.h:
+    storm_bss_sdr_rows has the definition and the edge rules: +inf for no rest, NaN for an empty or all-zero row and for a reference whose
+    delays are numerically dependent).  lengths: per-row sample counts of a ragged batch (the rest of a row is not read).
+    return_filter adds fp64 [B, flen], the solved filter (argmax |filter| is the estimate's delay); return_parts adds fp64 [B, 2 flen + 1] =
+    (G, D, Ee), the correlations it was solved from.  Two launches, no synchronisation; a row's outputs do not depend on the batch it is in."""
+    ref, est = _wave_rows("bss_sdr_rows", "reference", reference), _wave_rows("bss_sdr_rows", "estimate", estimate)
+    B, Lw = ref.shape
+    if est.shape != ref.shape:
+        raise ValueError(f"bss_sdr_rows: {tuple(ref.shape)} against {tuple(est.shape)}")
+    if lengths is not None:                                        # (a row of no samples is allowed here: its SDR is NaN)
+        vals = [int(v) for v in lengths]
+        if len(vals) != B or min(vals) < 0 or max(vals) > Lw:
+            raise ValueError(f"bss_sdr_rows: lengths {vals} for a batch of {B} rows x {Lw}")
+    flen = int(flen)
+    out = _alloc((B,), torch.float64, ref)
+    filt = _alloc((B, max(flen, 1)), torch.float64, ref) if return_filter else None
+    parts = _alloc((B, 2 * max(flen, 0) + 1), torch.float64, ref) if return_parts else None
+    ws = torch.empty((max(L.lib().storm_bss_sdr_scratch_bytes(B, Lw, flen) // 8, 1),), dtype=torch.float64, device=ref.device)
+    sr, se = (ref.stride(0), est.stride(0)) if B > 1 else (Lw, Lw)    # (a one-row tensor's row stride is whatever its producer left there)
+    rl = _row_len(lengths, ref)
+    L.check(L.lib().storm_bss_sdr_rows(L.ptr_rows(ref), L.ptr_rows(est), L.ptr(out), L.ptr(filt), L.ptr(parts), L.ptr(ws), 8 * ws.numel(), B, Lw,
+                                       sr, se, L.ptr(rl), flen, L.stream()), "storm_bss_sdr_rows")
+    res = (out,) + ((filt,) if return_filter else ()) + ((parts,) if return_parts else ())
+    return res if len(res) > 1 else out
+
+
 # ---------------------------------------------------------------- ConvTasNet --------------
 TASNET_ENCODE, TASNET_POINTWISE, TASNET_DEPTHWISE = 0, 1, 2
 

@@ -34,7 +34,7 @@ def _optional(name, attr):
 METRIC_KEYS = ("si_sdr", "si_sir", "si_sar", "lsd", "isnr")
 
 
-def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, align=False, max_lag=None, hp=None):
+def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, align=False, max_lag=None, hp=None, sdr=False, sdr_taps=512):
     """The calc_metrics numbers of one micro-batch of device waveforms [B, L]: a dict of fp64 [B] tensors si_sdr / si_sir / si_sar
     (energy_ratios(estimate, clean, noisy - clean), util/other.py:35-44), lsd (estimate against clean, :16-19) and isnr (snr_dB(clean,
     noisy - clean), :96-100).  lengths: per-row sample counts of a ragged batch.  One energy launch pair, two STFTs and one LSD launch
@@ -44,7 +44,8 @@ def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, alig
     to fp32 once).  align=True: the estimate is then moved onto the clean row by the arg-max of their cross-correlation
     (ops.xcorr_lag_rows, |lag| <= max_lag samples when given) and ZERO-FILLED, not rolled - rolled-in samples are unrelated audio that would
     enter every energy - before any metric; the result gains the key lag (int32 [B]): the samples by which the estimate was late.
-    Without the three keywords nothing changes."""
+    sdr=True adds the key sdr: the BSS-eval SDR of the estimate against clean with a filter of sdr_taps taps (ops.bss_sdr_rows), computed on
+    what hp= and align= leave.  Without these keywords nothing changes."""
     from .. import ops
     clean, noisy, estimate = clean.float(), noisy.float(), estimate.float()
     if hp is not None:
@@ -59,6 +60,8 @@ def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, alig
     if stoi:
         d = ops.stoi_rows(clean, estimate, lengths=lengths, fs=fs)
         out["stoi"], out["estoi"] = d[:, 0], d[:, 1]
+    if sdr:
+        out["sdr"] = ops.bss_sdr_rows(clean, estimate, lengths=lengths, flen=sdr_taps)
     if lag is not None:
         out["lag"] = lag
     return out

@@ -1,7 +1,8 @@
 """Small utilities of sgmse/util/other.py that the hot path and the evaluation loop use:
 pad_spec (:102-109), si_sdr / si_sdr_torch (:82-94), and the metrics of the calc_metrics step in batch form on the device:
 energy_ratios (:21-44), lsd (:16-19), snr_dB (:96-100); mean_std (:53-57) on the host; stoi: STOI / ESTOI on the device under the
-signature of pystoi.stoi, which the reference's evaluation calls; align (:153-157) and hp_filter (:76-80) on the device."""
+signature of pystoi.stoi, which the reference's evaluation calls; align (:153-157) and hp_filter (:76-80) on the device; sdr: the BSS-eval SDR with a short filter,
+which the reference does not have."""
 import warnings
 
 import numpy as np
@@ -139,6 +140,18 @@ def hp_filter(signal, cut_off=80, order=10, sr=16000, lengths=None):
     (x,), one = _device_rows(signal)
     out = ops.sosfilt_rows(x, ops.butter_sos(order, cut_off / sr * 2, "hp"), lengths=lengths, out_dtype=torch.float64)
     return out[0] if one else out
+
+
+def sdr(s, s_hat, flen=512, lengths=None):
+    """BSS-eval SDR in dB of the estimate s_hat against the clean s, in si_sdr's argument order, on the device: s_hat is allowed any linear
+    filter of `flen` taps of s (a delay, a codec's or a resampler's colouring), where si_sdr allows a gain (storm_bss_sdr_rows;
+    include/storm_hip.h has the definition - the reference has no such metric, and nothing here was compared with mir_eval).  s, s_hat: 1-D ->
+    a float; [B, L] -> an fp64 tensor [B] on the device (lengths: per-row sample counts of a ragged batch).  numpy arrays are moved to the
+    current HIP device; fp32 is what the kernels read."""
+    from .. import ops
+    (sr, er), one = _device_rows(s, s_hat)
+    d = ops.bss_sdr_rows(sr, er, lengths=lengths, flen=flen)
+    return float(d[0]) if one else d
 
 
 def mean_std(data):
