@@ -206,6 +206,25 @@ inline hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return 1; }
 //   STORM_SIM_DMA=late  : a copy lands only when the issuing lane's counted vm_wait<N> retires it (in issue order,
 //                         leaving the N newest in flight)        -> exposes read-after-write hazards (a fragment read
 //                         before the wait + barrier that publishes the data).
+//
+// ---- wave schedules (simrt.cpp::run_block) -------------------------------------------------------------------------------
+// The second timing knob: which wave of a workgroup gets ahead of which.  A yield point is an MFMA, a shuffle, wave_sync,
+// vm_wait or a barrier.  STORM_SIM_WAVES, read once per loaded library like STORM_SIM_DMA:
+//   unset     : an ascending sweep - every wave advances one yield point per turn, low waves first;
+//   reverse   : the same sweep with the waves in descending order  -> a low wave's LDS write that a higher wave reads with
+//               no barrier between them;
+//   first     : the lowest wave runs ahead: one runnable fiber of the lowest wave that has one is resumed, then the choice
+//               is made again, so the other waves move only when every lower wave waits at a workgroup barrier or has
+//               finished  -> hazards that need a whole barrier interval of skew (a ring slot refilled, or a patch rewritten,
+//               while a slow wave still reads it);
+//   last      : the same with the highest wave;
+//   seed:<n>  : before each resume the wave is drawn by a counter-based generator of (n, workgroup id, step): a failure
+//               replays from its seed alone.
+// In every mode the lanes of a wave keep ascending order (hardware lanes run in lockstep; a lane that reads another lane's
+// LDS needs a rendezvous here anyway), collectives and __syncthreads keep their meaning, and a schedule is private to its
+// workgroup.  The schedules bracket wave order and phase skew INSIDE a workgroup; they say nothing about lanes inside a wave,
+// ordering between workgroups, or what the compiler does to the real ISA.  tests/sim/hazard_zoo.cpp holds the kernels that
+// prove which mistake each mode catches (tests/test_sim_schedules.py).
 namespace simdma {
 struct Entry { char* dst; char data[16]; };
 inline bool late() { static const bool v = [] { const char* e = getenv("STORM_SIM_DMA"); return e && e[0] == 'l'; }(); return v; }

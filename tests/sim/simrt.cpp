@@ -31,6 +31,72 @@ void fiber_main() {
     swapcontext(&me.ctx, &B.sched);
 }
 
+// ---- wave schedules (STORM_SIM_WAVES, documented in hip_host_shim.h) ----------------------------------------------------
+enum { ASCENDING = 0, REVERSE, FIRST, LAST, SEEDED };
+struct Sched { int mode; uint64_t seed; };
+const Sched& sched() {                                   // read once per loaded library, like STORM_SIM_DMA
+    static const Sched v = [] {
+        const char* e = getenv("STORM_SIM_WAVES");
+        if (!e || !e[0]) return Sched{ASCENDING, 0};
+        if (!strcmp(e, "reverse")) return Sched{REVERSE, 0};
+        if (!strcmp(e, "first")) return Sched{FIRST, 0};
+        if (!strcmp(e, "last")) return Sched{LAST, 0};
+        if (!strncmp(e, "seed:", 5) && e[5]) { char* end; const uint64_t n = strtoull(e + 5, &end, 10); if (!*end) return Sched{SEEDED, n}; }
+        fprintf(stderr, "simrt: STORM_SIM_WAVES=%s is none of reverse / first / last / seed:<n>\n", e);
+        abort();
+    }();
+    return v;
+}
+inline uint64_t mix(uint64_t x) {                        // splitmix64's finaliser: the counter-based generator of the seeded schedule
+    x += 0x9e3779b97f4a7c15ull; x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull; x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+// lowest runnable lane of a wave, or -1 (lanes keep ascending order in every schedule)
+inline int runnable(const Block& B, int w) {
+    const int end = std::min(B.nthreads, 64 * w + 64);
+    for (int i = 64 * w; i < end; ++i) if (B.f[i].state == RUN) return i;
+    return -1;
+}
+inline bool release_barrier(Block& B) {
+    if (B.n_barrier == 0 || B.n_barrier != B.nthreads - B.n_done) return false;
+    for (auto& f : B.f) if (f.state == WAIT_BLOCK) f.state = RUN;
+    B.n_barrier = 0;
+    return true;
+}
+// The schedules other than the ascending sweep.  All state is in B and on this stack: workgroups run on several OS threads.
+void run_skewed(Block& B, const Sched& sc, int nw) {
+    const uint64_t blk = B.bid.x + (uint64_t)B.grid.x * (B.bid.y + (uint64_t)B.grid.y * B.bid.z);
+    uint64_t step = 0;
+    while (B.n_done < B.nthreads) {
+        bool progressed = false;
+        if (sc.mode == REVERSE) {                        // the sweep with waves in descending order
+            for (int w = nw - 1; w >= 0; --w)
+                for (int i = 64 * w, end = std::min(B.nthreads, 64 * w + 64); i < end; ++i) {
+                    if (B.f[i].state != RUN) continue;
+                    B.cur = i;
+                    swapcontext(&B.sched, &B.f[i].ctx);
+                    progressed = true;
+                }
+        } else {                                         // one fiber of the chosen wave, then choose again
+            int pick = -1;
+            if (sc.mode == FIRST) { for (int w = 0; w < nw && pick < 0; ++w) pick = runnable(B, w); }
+            else if (sc.mode == LAST) { for (int w = nw - 1; w >= 0 && pick < 0; --w) pick = runnable(B, w); }
+            else {
+                int cand[16], nc = 0;                    // (a workgroup has at most 1024 threads)
+                for (int w = 0; w < nw; ++w) { const int i = runnable(B, w); if (i >= 0) cand[nc++] = i; }
+                if (nc) pick = cand[mix(mix(sc.seed ^ mix(blk)) + step++) % (uint64_t)nc];
+            }
+            if (pick >= 0) {
+                B.cur = pick;
+                swapcontext(&B.sched, &B.f[pick].ctx);
+                continue;
+            }
+        }
+        if (release_barrier(B)) progressed = true;
+        if (!progressed) { fprintf(stderr, "simrt: deadlock (divergent barrier / collective?)\n"); abort(); }
+    }
+}
+
 void run_block(Block& B) {
     g_blk = &B;
     if (g_stacks.size() < STACK * (size_t)B.nthreads) g_stacks.resize(STACK * (size_t)B.nthreads);
@@ -49,6 +115,8 @@ void run_block(Block& B) {
     B.waves.assign(nw, Wave());
     for (int w = 0; w < nw; ++w) { B.waves[w].arrived = 0; B.waves[w].ndone = 0; B.waves[w].nlanes = std::min(64, B.nthreads - 64 * w); }
     B.n_done = 0; B.n_barrier = 0;
+    const Sched sc = sched();
+    if (sc.mode != ASCENDING) { run_skewed(B, sc, nw); g_blk = nullptr; return; }
     while (B.n_done < B.nthreads) {
         bool progressed = false;
         for (int i = 0; i < B.nthreads; ++i) {
