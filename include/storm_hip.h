@@ -694,8 +694,7 @@ int storm_butter_sos(int order, double wn, int highpass, double* sos_out);
  * at some order - a reference whose F delays are numerically dependent; mir_eval falls back to a least-squares solve there, this refuses
  * by NaN.  No diagonal loading is applied (band-limited references down to min E / G[0] = 5e-5 solve to the same SDR as a dense solver).
  * The filter of a NaN row is NaN; the correlations of a row of fewer than 1 sample are zeros.  Samples are expected finite.
- * Out of scope: SIR / SAR against a noise reference (a block-Toeplitz system of twice the size, not a Levinson problem), a time-varying
- * filter, permutations of several sources.
+ * SIR / SAR against a noise reference: storm_bss_eval_rows below.  Out of scope: a time-varying filter, permutations of several sources.
  *
  * storm_bss_sdr_scratch_bytes: device scratch for rows of L samples: B * ceil(L / STORM_BSS_PIECE) * (2 flen + 1) doubles (0: refused -
  *   B outside 1 .. 65535, L outside 1 .. 2^30, flen outside 1 .. STORM_BSS_MAX_TAPS).
@@ -709,6 +708,68 @@ int storm_butter_sos(int order, double wn, int highpass, double* sos_out);
 long long storm_bss_sdr_scratch_bytes(int B, long long L, int flen);
 int storm_bss_sdr_rows(const float* ref, const float* est, double* sdr, double* filt, double* parts, void* scratch, long long scratch_bytes,
                        int B, long long L, long long stride_ref, long long stride_est, const int* row_len, int flen, storm_stream_t st);
+
+/* ------------------------------------------------------------------------------------------
+ * BSS-eval SDR, SIR and SAR with two sources (bss_eval_sources of Vincent, Gribonval, Fevotte 2006 for target and noise): the distortion
+ * of an estimate that may be a FILTERED mixture is split into "noise that is left" (SIR) and "what the system invented" (SAR).  This is
+ * BSS-eval's split: the projection onto the delayed copies of BOTH sources is JOINT, and SAR's numerator is s_target + e_interf.  It is NOT
+ * the reference project's si_sir / si_sar (storm_energy_ratios_rows), which use two separate one-tap projections and put the target alone in
+ * SAR's numerator, and so book any filter as interference and artefacts.  The reference project does not compute it: this comment is the
+ * specification.
+ *
+ * Per row: target s1[0..L), interferer s2[0..L), estimate e[0..L), all fp32; F = flen, 1 <= F <= STORM_BSS_MAX_TAPS.
+ *
+ * Correlations, for k = 0 .. F - 1:
+ *   G11[k] = sum s1[n] s1[n + k]     D1[k] = sum s1[n] e[n + k]
+ *   G22[k] = sum s2[n] s2[n + k]     D2[k] = sum s2[n] e[n + k]
+ *   X12[k] = sum s1[n] s2[n + k]     X21[k] = sum s2[n] s1[n + k]        Ee = sum e[n]^2
+ * every one summed exactly as above: exact fp64 products, pieces of STORM_BSS_PIECE samples cut by the index of the FIRST factor, inside a
+ * piece one ascending fp64 chain from +0, the pieces added in order, no atomics.  These 6 F + 1 numbers are, bit for bit, what four calls of
+ * storm_bss_sdr_rows return as parts: (ref, est) = (s1, e), (s2, e), (s1, s2), (s2, s1).  parts is fp64 [B][6 F + 1] in the order
+ * G11, D1, G22, D2, X12, X21, Ee.
+ *
+ * Joint system.  The unknowns are interleaved, x = (c1[0], c2[0], c1[1], c2[1], ..).  M is 2 F x 2 F, symmetric, block-Toeplitz with 2 x 2
+ * blocks:
+ *   block(k, l) = R(k - l)     R(m) = [[G11[|m|], c12(m)], [c12(-m), G22[|m|]]]     c12(m) = X12[m] for m >= 0, X21[-m] for m < 0
+ * - the Gram matrix of the 2 F zero-padded delayed copies.  d = (D1[0], D2[0], D1[1], ..).  M x = d is solved in fp64 and P12 = d . x.
+ * P1 = D1 . C1 with Toeplitz(G11) C1 = D1 is the single-source projection above, by the same recursion in the same summation shape.
+ *
+ * The solve is the block Levinson recursion (Whittle 1963; Wiggins & Robinson 1965) with 2 x 2 blocks: forward predictor A, backward
+ * predictor B (kept reversed, Bt_j = B_{m - j}), symmetric 2 x 2 error matrices Ef, Eb, all starting from I and R(0); x[0] = R(0)^-1 d[0].
+ *   for m = 1 .. F - 1:
+ *       Delta = sum_{j<m} R(m - j) A_j          delta = sum_{j<m} R(m - j) x_j
+ *       Kf = -Eb^-1 Delta                       Kb = -Ef^-1 Delta^T
+ *       A_j <- A_j + Bt_{m-j} Kf                Bt_j <- Bt_j + A_{m-j} Kb         (j = 0 .. m, the old values on the right)
+ *       Ef <- Ef + Delta^T Kf                   Eb <- Eb + Delta Kb               (the two off-diagonal entries averaged)
+ *       g = Eb^-1 (d[m] - delta)                x_j <- x_j + Bt_{m-j} g           (the new Eb and Bt)
+ * A 2 x 2 matrix [[a, b], [b, c]] is inverted through l = b / a, p = c - l b (its pivots a and p).  Every multiply-add is a fused one; the
+ * six sums of an order have the shape of the recursion above: block j in lane j mod 64 of one wave, a lane's blocks j < m as fma chains in
+ * ascending j from +0 (inside a block first the column of s1, then that of s2), then the xor butterfly 32 .. 1.  Fixed, so rows stay
+ * batch-independent; pinned by bounds against dense solvers, NOT bit for bit.  This recursion was built, and not a blocked Cholesky of the
+ * dense matrix in global scratch, because it meets the bound (1e-4 dB against two dense host solvers up to a joint condition of 1e8) inside
+ * one wave's registers and 56 KB of LDS.
+ *
+ * Numbers (out fp64 [B][3]):
+ *   sdr = 10 log10(P1 / (Ee - P1))      the SAME BITS as storm_bss_sdr_rows(s1, e)
+ *   sir = 10 log10(P1 / (P12 - P1))
+ *   sar = 10 log10(P12 / (Ee - P12))
+ * Edge rules.  P12 - P1 <= 0 with P1 > 0: sir = +inf (P1 <= 0 then: NaN; P1 <= 0 otherwise: -inf).  Ee - P12 <= 0: sar = +inf (else
+ * P12 <= 0: -inf).  Whatever makes the SDR above NaN makes all three NaN.  G22[0] == 0 (a silent noise row): sir and sar are NaN, sdr is still
+ * given.  A joint system that is numerically dependent - a pivot a or p of Ef or Eb that is <= 0 or not finite at some order, e.g. a noise row
+ * that is a multiple or a filtered copy of the target - : sir and sar are NaN; no diagonal loading, no least-squares fallback.  A row of
+ * fewer than F + 1 samples is always dependent (2 F zero-padded copies in L + F - 1 dimensions) and is refused the same way by its length,
+ * not by the rounding of a pivot that is zero in exact arithmetic; its sdr is still given.  filt
+ * (optional) fp64 [B][2][F] = c1, c2 of the joint solve, NaN where sir is NaN.  The correlations of a row of no samples are zeros.
+ * Out of scope: permutations of several sources, a time-varying filter.
+ *
+ * storm_bss_eval_scratch_bytes: 4 x storm_bss_sdr_scratch_bytes(B, L, flen) + 8 B bytes (0: refused, as there).
+ * storm_bss_eval_rows: three launches - the four pairs' correlations as one grid (a workgroup per (pair, row, piece), the walk of
+ *   storm_bss_sdr_rows), that entry's solve for sdr and P1, one wave per row for the joint recursion.  Strides in floats, row_len and scratch
+ *   as above. */
+long long storm_bss_eval_scratch_bytes(int B, long long L, int flen);
+int storm_bss_eval_rows(const float* target, const float* noise, const float* est, double* out, double* filt, double* parts, void* scratch,
+                        long long scratch_bytes, int B, long long L, long long stride_t, long long stride_n, long long stride_e,
+                        const int* row_len, int flen, storm_stream_t st);
 
 /* ------------------------------------------------------------------------------------------
  * ConvTasNet (backbones/convtasnet.py): the time-domain denoiser.  Activations are channels-last [B][L][C] in `dtype`

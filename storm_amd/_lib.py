@@ -171,6 +171,8 @@ _SIGNATURES = {
     "storm_butter_sos": ([_i, C.c_double, _i, _vp], C.c_int),
     "storm_bss_sdr_scratch_bytes": ([_i, _ll, _i], C.c_longlong),
     "storm_bss_sdr_rows": ([_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _vp, _i, _vp], C.c_int),
+    "storm_bss_eval_scratch_bytes": ([_i, _ll, _i], C.c_longlong),
+    "storm_bss_eval_rows": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _ll, _vp, _i, _vp], C.c_int),
     "storm_tasnet_num_partials":([_i, _i, _i], C.c_int),
     "storm_tasnet_frames": ([_ll, _i], C.c_int),
     "storm_tasnet_encode": ([_vp, _ll, _vp, _vp, _vp, _i, _ll, _i, _i, _i, _vp], C.c_int),

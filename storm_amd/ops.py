@@ -1158,6 +1158,35 @@ def bss_sdr_rows(reference, estimate, lengths=None, flen=512, return_filter=Fals
     return res if len(res) > 1 else out
 
 
+def bss_eval_rows(target, noise, estimate, lengths=None, flen=512, return_filter=False, return_parts=False):
+    """fp64 [B, 3] = (sdr, sir, sar) in dB per row of three fp32 waveform batches [B, L] (rows may be strided views): BSS-eval with two
+    sources - the estimate projected onto `flen` delayed copies of the target (P1) and, jointly, of target and noise (P12); sdr = P1 / (Ee -
+    P1) is bss_sdr_rows(target, estimate) bit for bit, sir = P1 / (P12 - P1), sar = P12 / (Ee - P12) (include/storm_hip.h:
+    storm_bss_eval_rows has the definition and the edge rules: NaN sir / sar for a silent noise row and for a noise row whose delays depend
+    on the target's).  This is BSS-eval's split, not si_sir / si_sar of energy_ratios_rows.  lengths: per-row sample counts of a ragged batch.
+    return_filter adds fp64 [B, 2, flen], the two filters of the joint solve; return_parts adds fp64 [B, 6 flen + 1] = (G11, D1, G22, D2,
+    X12, X21, Ee).  Three launches, no synchronisation; a row's outputs do not depend on the batch it is in."""
+    tgt, noi, est = (_wave_rows("bss_eval_rows", n, v) for n, v in (("target", target), ("noise", noise), ("estimate", estimate)))
+    B, Lw = tgt.shape
+    if est.shape != tgt.shape or noi.shape != tgt.shape:
+        raise ValueError(f"bss_eval_rows: {tuple(tgt.shape)}, {tuple(noi.shape)} and {tuple(est.shape)}")
+    if lengths is not None:                                        # (a row of no samples is allowed here: its numbers are NaN)
+        vals = [int(v) for v in lengths]
+        if len(vals) != B or min(vals) < 0 or max(vals) > Lw:
+            raise ValueError(f"bss_eval_rows: lengths {vals} for a batch of {B} rows x {Lw}")
+    flen = int(flen)
+    out = _alloc((B, 3), torch.float64, tgt)
+    filt = _alloc((B, 2, max(flen, 1)), torch.float64, tgt) if return_filter else None
+    parts = _alloc((B, 6 * max(flen, 0) + 1), torch.float64, tgt) if return_parts else None
+    ws = torch.empty((max(L.lib().storm_bss_eval_scratch_bytes(B, Lw, flen) // 8, 1),), dtype=torch.float64, device=tgt.device)
+    st, sn, se = (tgt.stride(0), noi.stride(0), est.stride(0)) if B > 1 else (Lw, Lw, Lw)
+    rl = _row_len(lengths, tgt)
+    L.check(L.lib().storm_bss_eval_rows(L.ptr_rows(tgt), L.ptr_rows(noi), L.ptr_rows(est), L.ptr(out), L.ptr(filt), L.ptr(parts), L.ptr(ws),
+                                        8 * ws.numel(), B, Lw, st, sn, se, L.ptr(rl), flen, L.stream()), "storm_bss_eval_rows")
+    res = (out,) + ((filt,) if return_filter else ()) + ((parts,) if return_parts else ())
+    return res if len(res) > 1 else out
+
+
 # ---------------------------------------------------------------- ConvTasNet --------------
 TASNET_ENCODE, TASNET_POINTWISE, TASNET_DEPTHWISE = 0, 1, 2
 

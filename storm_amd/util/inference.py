@@ -34,7 +34,8 @@ def _optional(name, attr):
 METRIC_KEYS = ("si_sdr", "si_sir", "si_sar", "lsd", "isnr")
 
 
-def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, align=False, max_lag=None, hp=None, sdr=False, sdr_taps=512):
+def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, align=False, max_lag=None, hp=None, sdr=False, sdr_taps=512, bss=False,
+                bss_taps=512):
     """The calc_metrics numbers of one micro-batch of device waveforms [B, L]: a dict of fp64 [B] tensors si_sdr / si_sir / si_sar
     (energy_ratios(estimate, clean, noisy - clean), util/other.py:35-44), lsd (estimate against clean, :16-19) and isnr (snr_dB(clean,
     noisy - clean), :96-100).  lengths: per-row sample counts of a ragged batch.  One energy launch pair, two STFTs and one LSD launch
@@ -45,7 +46,9 @@ def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, alig
     (ops.xcorr_lag_rows, |lag| <= max_lag samples when given) and ZERO-FILLED, not rolled - rolled-in samples are unrelated audio that would
     enter every energy - before any metric; the result gains the key lag (int32 [B]): the samples by which the estimate was late.
     sdr=True adds the key sdr: the BSS-eval SDR of the estimate against clean with a filter of sdr_taps taps (ops.bss_sdr_rows), computed on
-    what hp= and align= leave.  Without these keywords nothing changes."""
+    what hp= and align= leave.  bss=True adds the keys bss_sdr, bss_sir, bss_sar: BSS-eval with two sources, target clean and noise noisy -
+    clean, each allowed a filter of bss_taps taps, solved jointly (ops.bss_eval_rows; BSS-eval's split, not si_sir / si_sar), on the same
+    rows.  Without these keywords nothing changes."""
     from .. import ops
     clean, noisy, estimate = clean.float(), noisy.float(), estimate.float()
     if hp is not None:
@@ -62,6 +65,9 @@ def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, alig
         out["stoi"], out["estoi"] = d[:, 0], d[:, 1]
     if sdr:
         out["sdr"] = ops.bss_sdr_rows(clean, estimate, lengths=lengths, flen=sdr_taps)
+    if bss:
+        d = ops.bss_eval_rows(clean, noisy - clean, estimate, lengths=lengths, flen=bss_taps)
+        out["bss_sdr"], out["bss_sir"], out["bss_sar"] = d[:, 0], d[:, 1], d[:, 2]
     if lag is not None:
         out["lag"] = lag
     return out

@@ -154,6 +154,18 @@ def sdr(s, s_hat, flen=512, lengths=None):
     return float(d[0]) if one else d
 
 
+def bss_eval(s, n, s_hat, flen=512, lengths=None):
+    """(sdr, sir, sar) in dB of the estimate s_hat against the clean s and the noise n, in energy_ratios' argument roles, on the device:
+    BSS-eval with two sources - s_hat is allowed one linear filter of `flen` taps of s and one of n, solved jointly; sir is what is left of n,
+    sar what neither source explains (storm_bss_eval_rows; include/storm_hip.h has the definition - this is BSS-eval's split, not si_sir /
+    si_sar, and nothing here was compared with mir_eval).  1-D arguments -> three floats; [B, L] -> three fp64 tensors [B] on the device
+    (lengths: per-row sample counts of a ragged batch).  numpy arrays are moved to the current HIP device; fp32 is what the kernels read."""
+    from .. import ops
+    (sr, nr, er), one = _device_rows(s, n, s_hat)
+    d = ops.bss_eval_rows(sr, nr, er, lengths=lengths, flen=flen)
+    return tuple(float(d[0, k]) for k in range(3)) if one else (d[:, 0], d[:, 1], d[:, 2])
+
+
 def mean_std(data):
     """(mean, population std) of the values that are not NaN (util/other.py:53-57); host"""
     data = np.asarray(data.detach().cpu() if isinstance(data, torch.Tensor) else data, dtype=np.float64)
