@@ -459,11 +459,15 @@ int storm_complex_randn_rs(float* z, int B, long long n_per_row, uint64_t seed, 
  * 102-109) and the peak normalisation in enhance() (model.py:282-284, 302).
  * ------------------------------------------------------------------------------------------ */
 /* out = spec_fwd(in) (inverse==0) or spec_back(in) (inverse!=0) on n complex64 values
- * (data_module.py:182-193): |z|^e e^{j angle z} * factor  /  its inverse.                  */
+ * (data_module.py:182-193): |z|^e e^{j angle z} * factor  /  its inverse.  An exact-zero bin stays exactly zero in both
+ * directions.  |z| is sqrtf(re^2 + im^2) while re^2 + im^2 lies in [2^-100, 2^100] and hypotf(re, im) outside, where the squares
+ * under- or overflow and torch.abs does not (here, in storm_stft and in storm_istft alike).  */
 int storm_spec_transform(const float* in, float* out, long long n_complex, float spec_factor,
                          float spec_abs_exponent, int inverse, storm_stream_t s);
 /* Ragged batches (micro-batching of utterances of different lengths that share ONE padded frame count, i.e.
- * roundup(1 + L_b / hop, 64) equal for all rows): the three front / back end calls take row_len = device int32 [B] with
+ * roundup(frames(L_b), 64) equal for all rows, frames(L) = 1 + (L + 2 (n_fft / 2) - n_fft) / hop in integer division: torch.stft's
+ * count with center=True, which is 1 + L / hop for an even n_fft and 1 + (L - 1) / hop for an odd one; storm_stft takes
+ * n_frames = frames(L) and refuses another value): the three front / back end calls take row_len = device int32 [B] with
  * every row's own sample count (NULL = all rows L); wav buffers are [B][L] with L = the longest row, zero filled past a
  * row's length.  Row b then equals the single-utterance call with L_b (the reference pads per utterance,
  * util/other.py:102-109, enhancement.py:66-72).

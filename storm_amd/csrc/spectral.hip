@@ -12,6 +12,18 @@ namespace storm {
 
 constexpr int MAX_NFFT = 1024;
 
+// frames of torch.stft(center=True) over L samples: the row grows by n_fft / 2 (rounded down) on either side, and every frame needs n_fft
+// samples of it.  Even n_fft: 1 + L / hop.  Odd n_fft: 1 + (L - 1) / hop, one frame fewer whenever hop divides L.
+__host__ __device__ inline long long stft_frames(long long L, int n_fft, int hop) { return 1 + (L + 2 * (n_fft / 2) - n_fft) / hop; }
+
+// |z| of a spectrogram bin for spec_fwd / spec_back.  sqrtf(re^2 + im^2) wherever the sum of squares is far from fp32's ends (the bits this
+// library has always produced); outside that range the squares underflow or overflow where torch.abs does not (a bin of magnitude 1e-30
+// came out as 0), so there hypotf takes over.
+__device__ inline float spec_abs(float re, float im) {
+    const float s = re * re + im * im;
+    return (s >= 0x1p-100f && s <= 0x1p+100f) ? sqrtf(s) : hypotf(re, im);
+}
+
 __global__ void peak_abs_kernel(const float* __restrict__ wav, float* __restrict__ peak, long long L, long long stride,
                                 const int* __restrict__ row_len) {
     __shared__ float red[4];
@@ -35,7 +47,7 @@ __global__ void stft_kernel(const float* __restrict__ wav, const float* __restri
     __shared__ float2 tws[MAX_NFFT];
     const int frame = blockIdx.x, b = blockIdx.y, F = n_fft / 2 + 1;
     float2* out = reinterpret_cast<float2*>(spec) + (long long)b * F * Tpad;
-    if (row_len) { L = row_len[b]; n_frames = 1 + (int)(L / hop); }      // ragged batch: this row's own length / frame count
+    if (row_len) { L = row_len[b]; n_frames = (int)stft_frames(L, n_fft, hop); }      // ragged batch: this row's own length / frame count
     if (frame >= n_frames) {                       // pad_spec: zero frames
         for (int f = threadIdx.x; f < F; f += blockDim.x) out[(long long)f * Tpad + frame] = make_float2(0.f, 0.f);
         return;
@@ -66,7 +78,7 @@ __global__ void stft_kernel(const float* __restrict__ wav, const float* __restri
         float zr = (float)re, zi = (float)im;
         // spec_fwd: |X|^e exp(j angle X) * factor  (data_module.py:182-186)
         if (expo != 1.0f) {
-            const float mag = sqrtf(zr * zr + zi * zi);
+            const float mag = spec_abs(zr, zi);
             const float sc = mag > 0.f ? powf(mag, expo - 1.0f) : 0.f;
             zr *= sc; zi *= sc;
         }
@@ -85,7 +97,7 @@ __global__ void istft_frames_kernel(const float* __restrict__ spec, float* __res
         float2 z = in[(long long)f * T + frame];
         z.x /= factor; z.y /= factor;                         // spec_back (data_module.py:188-193)
         if (expo != 1.0f) {
-            const float mag = sqrtf(z.x * z.x + z.y * z.y);
+            const float mag = spec_abs(z.x, z.y);
             const float sc = mag > 0.f ? powf(mag, 1.0f / expo - 1.0f) : 0.f;
             z.x *= sc; z.y *= sc;
         }
@@ -136,7 +148,7 @@ __global__ void spec_transform_kernel(const float* __restrict__ in, float* __res
         float2 z = reinterpret_cast<const float2*>(in)[i];
         if (inverse) { z.x /= factor; z.y /= factor; }
         if (expo != 1.0f) {
-            const float mag = sqrtf(z.x * z.x + z.y * z.y);
+            const float mag = spec_abs(z.x, z.y);
             const float sc = mag > 0.f ? powf(mag, (inverse ? 1.0f / expo : expo) - 1.0f) : 0.f;
             z.x *= sc; z.y *= sc;
         }
@@ -253,7 +265,7 @@ extern "C" int storm_stft(const float* wav, const float* peak, float* spec, cons
     STORM_CHECK(wav && spec && window && twiddle && B > 0, "storm_stft: null pointer");
     STORM_CHECK(n_fft >= 2 && n_fft <= MAX_NFFT && hop > 0, "storm_stft: n_fft=%d hop=%d", n_fft, hop);
     STORM_CHECK(L > n_fft / 2, "storm_stft: signal too short for reflect padding (L=%lld)", L);
-    STORM_CHECK(n_frames == 1 + (int)(L / hop) && Tpad >= n_frames, "storm_stft: n_frames=%d Tpad=%d L=%lld", n_frames, Tpad, L);
+    STORM_CHECK(n_frames == (int)stft_frames(L, n_fft, hop) && Tpad >= n_frames, "storm_stft: n_frames=%d Tpad=%d L=%lld", n_frames, Tpad, L);
     hipLaunchKernelGGL(stft_kernel, dim3(Tpad, B), dim3(256), 0, (hipStream_t)s, wav, peak, spec, window, twiddle, L, stride,
                        n_fft, hop, n_frames, Tpad, spec_factor, spec_abs_exponent, row_len);
     STORM_LAUNCH_CHECK();

@@ -56,8 +56,8 @@ class SpecsDataModule:
         """spec [C, F, T] (or [F, T]) complex64 -> [C, length]"""
         squeeze = spec.dim() == 2
         X = spec.unsqueeze(0) if squeeze else spec
-        if length is None:
-            length = self.hop_length * (X.shape[-1] - 1)
+        if length is None:                   # torch.istft's default: all n_fft + hop (T - 1) samples less n_fft // 2 at either end
+            length = self.n_fft + self.hop_length * (X.shape[-1] - 1) - 2 * (self.n_fft // 2)
         w = ops.istft(X.contiguous(), int(length), None, n_fft=self.n_fft, hop=self.hop_length, window=self.window_type)
         return w[0] if squeeze else w
 
@@ -78,7 +78,7 @@ class SpecsDataModule:
     # ---- fused batched forms used by enhance() ---------------------------------------------------
     def padded_frames(self, length, pad_to=64):
         """frames of one utterance after pad_spec (util/other.py:102-109): utterances with equal values can share a batch"""
-        return ops.round_up(1 + int(length) // self.hop_length, pad_to)
+        return ops.round_up(ops.stft_frames(length, self.n_fft, self.hop_length), pad_to)
 
     def wav_to_spec(self, wav, pad_to=64, lengths=None, peak=None):
         """wav [B, L] (rows may be a strided view) -> (Y [B,1,F,Tpad] = pad_spec(spec_fwd(stft(wav / peak))), peak [B])  in two launches.

@@ -136,14 +136,16 @@ def group_by_length(lengths, max_batch):
     return batches
 
 
-def bucket_by_frames(lengths, max_batch, hop=128, multiple=64):
+def bucket_by_frames(lengths, max_batch, hop=128, multiple=64, n_fft=510):
     """Micro-batches for utterances of DIFFERENT lengths: the reference pads every utterance's spectrogram to its own
     multiple of 64 frames (util/other.py:102-109), and every op of the path is per utterance, so utterances whose padded
-    frame count roundup(1 + L // hop, multiple) is equal can share a batch and still equal their single-utterance runs
-    (2-10 s at 16 kHz: 17 buckets).  Returns index lists (at most max_batch long), longest bucket first."""
+    frame count roundup(ops.stft_frames(L, n_fft, hop), multiple) is equal can share a batch and still equal their
+    single-utterance runs (2-10 s at 16 kHz: 17 buckets).  The frame count is 1 + L // hop for an even n_fft and
+    1 + (L - 1) // hop for an odd one.  Returns index lists (at most max_batch long), longest bucket first."""
+    from .ops import stft_frames
     by_t = {}
     for i, n in enumerate(lengths):
-        by_t.setdefault(-(-(1 + int(n) // hop) // multiple) * multiple, []).append(i)
+        by_t.setdefault(-(-stft_frames(n, n_fft, hop) // multiple) * multiple, []).append(i)
     batches = []
     for t in sorted(by_t, reverse=True):
         ids = sorted(by_t[t], key=lambda i: -int(lengths[i]))

@@ -367,7 +367,7 @@ class _Base(nn.Module):
                 rows = run[0][0][run[0][1]:run[0][1] + len(run)] if one_view else torch.stack([e[0][e[1]] for e in run])
                 jobs.append((rows, None, torch.cat([e[2] for e in run]), [e[3] for e in run], ("pool", j0)))
             lens = [x16[i].numel() for i in short_ids]
-            for bucket in bucket_by_frames(lens, int(batch), hop=dm.hop_length):
+            for bucket in bucket_by_frames(lens, int(batch), hop=dm.hop_length, n_fft=dm.n_fft):
                 bl = [lens[k] for k in bucket]
                 y = torch.zeros(len(bucket), max(bl), dtype=torch.float32, device=self.device)
                 for row, k in enumerate(bucket):

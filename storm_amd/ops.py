@@ -716,6 +716,12 @@ def peak_abs(wav, lengths=None):
     return out
 
 
+def stft_frames(length, n_fft, hop):
+    """frames of torch.stft(center=True) over `length` samples: the signal grows by n_fft // 2 samples on either side and every frame
+    needs n_fft samples of it.  Even n_fft: 1 + length // hop; odd n_fft: 1 + (length - 1) // hop."""
+    return 1 + (int(length) + 2 * (int(n_fft) // 2) - int(n_fft)) // int(hop)
+
+
 def stft(wav, peak=None, n_fft=510, hop=128, spec_factor=1.0, spec_abs_exponent=1.0, pad_to=1, window="hann", lengths=None):
     """wav [B, L] fp32 -> complex64 [B, n_fft/2+1, Tpad] = spec_fwd(stft(wav / peak)), zero padded
     in T to a multiple of `pad_to`.  lengths: per-row sample counts of a ragged batch (rows zero filled past them)."""
@@ -727,7 +733,7 @@ def stft(wav, peak=None, n_fft=510, hop=128, spec_factor=1.0, spec_abs_exponent=
         raise ValueError(f"stft: a row of {shortest} samples is too short for reflect padding by n_fft // 2 = {n_fft // 2}")
     if lengths is not None and int(max(int(v) for v in lengths)) > Lw:
         raise ValueError(f"stft: a row length exceeds the batch width {Lw}")
-    n_frames = 1 + Lw // hop
+    n_frames = stft_frames(Lw, n_fft, hop)
     Tpad = round_up(n_frames, pad_to)
     win, tw = dft_tables(n_fft, wav.device, window)
     spec = torch.empty((B, n_fft // 2 + 1, Tpad), dtype=torch.complex64, device=wav.device)

@@ -98,7 +98,7 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
     intel = torch.zeros(n, 2, dtype=torch.float64) if estoi == "device" else None
     hop = model.data_module.hop_length
     batched = hasattr(model, "enhance_batch") and not discriminative
-    for ids in bucket_by_frames([p[1].shape[-1] for p in pairs], batch if batched else 1, hop=hop):
+    for ids in bucket_by_frames([p[1].shape[-1] for p in pairs], batch if batched else 1, hop=hop, n_fft=model.data_module.n_fft):
         lens = [pairs[i][1].shape[-1] for i in ids]
         width = max(lens)
         y = torch.zeros(len(ids), width)
