@@ -150,6 +150,10 @@ const char* storm_conv_kernel_name(const storm_conv_args* a);
  * softmax-weighted sum unchanged (rows of the weights sum to one), or NULL.  bf16 / fp16 (P and the output rounded to the
  * operand type) and fp32 (exact-fp32 MFMA: the parity path), C in {32, 64, 128, 256}, any L; other cases return
  * STORM_ERR_UNSUPPORTED (storm_attention_supported tells beforehand) and run as GEMM + storm_softmax_rows.
+ * Alignment: the kernels read q, k and vT and write out in 16-byte pieces, so q, k, vT, out (and the scratch of storm_attention_ws) must
+ * be 16-byte aligned and the four batch strides - counted in elements, and free otherwise: rows of wider tensors are fine - multiples of
+ * 16 bytes (8 elements bf16 / fp16, 4 fp32); the same holds for every pointer of storm_attention_group.  bias has no requirement beyond
+ * a float's.  A call outside this is refused (STORM_ERR_INVALID, the argument named in storm_last_error) before anything is launched.
  * ------------------------------------------------------------------------------------------ */
 int storm_attention_supported(int C, int dtype);
 int storm_attention(const void* q, const void* k, const void* vT, const float* bias, void* out, int B, int L, int C, int ldv,

@@ -286,6 +286,17 @@ int attn_splits(int B, int L, int dtype) {
 }
 long long attn_scratch_bytes(int B, int L, int C, int S) { return S < 2 ? 0 : (long long)S * B * L * (C + 2) * 4; }
 
+// The alignment contract of include/storm_hip.h: every kernel above reads q, k and vT and writes out (and the split's scratch) in 16-byte
+// pieces at offsets that are multiples of 16 bytes from the batch item's base, so the bases and the batch strides must be too.  The name
+// of the first argument outside it (for the refusal), or nullptr.
+static const char* attn_misaligned(const void* q, const void* k, const void* vT, const void* out, long long q_bs, long long k_bs, long long v_bs,
+                                   long long o_bs, int dtype) {
+    const long long per16 = dtype == STORM_F32 ? 4 : 8;          // elements per 16 bytes
+    const auto off16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; };
+    return off16(q) ? "q" : off16(k) ? "k" : off16(vT) ? "vT" : off16(out) ? "out" : q_bs % per16 ? "q_bstride" : k_bs % per16 ? "k_bstride"
+         : v_bs % per16 ? "vT_bstride" : o_bs % per16 ? "out_bstride" : nullptr;
+}
+
 // ---- fp32 (parity path): the same online-softmax structure on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 sums).
 // Key tiles of 32 keys, K [32][C] and V^T [C][32] fp32 in LDS (2 x 32 KB at C = 256, double buffered = 128 KB), Q fragments of the
 // lane's query in registers (C / 2 floats: one 512-register wave per SIMD).  An MFMA contracts over two k-slots (the lane
@@ -512,6 +523,12 @@ extern "C" int storm_attention_ws(const void* q, const void* k, const void* vT, 
         set_error("storm_attention: C=%d dtype=%d is outside the fused kernel (use the GEMM + softmax path)", C, dtype);
         return STORM_ERR_UNSUPPORTED;
     }
+    if (const char* bad = attn_misaligned(q, k, vT, out, q_bstride, k_bstride, vT_bstride, out_bstride, dtype)) {
+        set_error("storm_attention: %s is outside the alignment contract (pointers 16-byte aligned, batch strides multiples of %d elements)", bad,
+                  dtype == STORM_F32 ? 4 : 8);
+        return STORM_ERR_INVALID;
+    }
+    STORM_CHECK((reinterpret_cast<uintptr_t>(scratch) & 15u) == 0, "storm_attention: scratch is outside the alignment contract (16-byte aligned)");
     hipStream_t st = (hipStream_t)s;
     if (dtype == STORM_F32) return attn_dispatch<float>(C, q, k, vT, bias, out, B, L, ldv, q_bstride, k_bstride, vT_bstride, out_bstride, scale, nullptr, 0, st);
     if (dtype == STORM_F16) return attn_dispatch<half_t>(C, q, k, vT, bias, out, B, L, ldv, q_bstride, k_bstride, vT_bstride, out_bstride, scale, scratch, scratch_bytes, st);
@@ -551,6 +568,11 @@ extern "C" int storm_attention_group(const void* const* q, const void* const* k,
     long long ni = 0;
     for (int g = 0; g < P; ++g) {
         STORM_CHECK(q[g] && k[g] && vT[g] && out[g] && B[g] > 0 && L[g] > 0 && ldv[g] >= L[g] && ldv[g] % 8 == 0, "storm_attention_group: problem %d", g);
+        // (the batch strides of a problem are L C and C ldv elements: multiples of 8 with the channel counts and ldv allowed here)
+        if (const char* bad = attn_misaligned(q[g], k[g], vT[g], out[g], 0, 0, 0, 0, dtype)) {
+            set_error("storm_attention_group: %s of problem %d is outside the alignment contract (pointers 16-byte aligned)", bad, g);
+            return STORM_ERR_INVALID;
+        }
         ni += attn_group_problem(g, q[g], k[g], vT[g], out[g], B[g], L[g], C, ldv[g], t[g], it + ni);
     }
     STORM_HIP(hipMemcpyAsync(blob, host.data(), (size_t)need, hipMemcpyHostToDevice, (hipStream_t)s));

@@ -134,7 +134,10 @@ COVERAGE = {
     "conv_narrow.hip": [OPS + "test_conv_narrow_output_kernel[sim-c256_gn_walk-dtype0]", OPS + "test_conv_narrow_output_kernel[sim-c256_two_planes-dtype1]",
                         OPS + "test_conv_group_narrow_output_equals_own_launches[sim-256-True-3]"],
     "attention.hip": [OPS + "test_fused_attention_key_split[sim-64-260-8-dt0-0.008]", OPS + "test_attention_group_equals_own_unsplit_calls[sim-dt0]",
-                      OPS + "test_fused_attention[sim-256-70-dt1-0.0015]"],
+                      OPS + "test_fused_attention[sim-256-70-dt1-0.0015]",
+                      # attention_f32_kernel's own staging and barriers, up to nine key tiles and three query blocks; the CT = 4 body, split
+                      "tests/test_attention_edges.py::test_rows_within_the_plain_restatement[sim-random-fp32-128-S1]",
+                      "tests/test_attention_edges.py::test_rows_within_the_plain_restatement[sim-flat-fp16-128-S2]"],
     "norm_resample.hip": [OPS + "test_groupnorm_fir_fused[sim-shape1-2-dtype1]", OPS + "test_groupnorm_fir_fused[sim-shape4-1-dtype1]",
                           OPS + "test_groupnorm_fir_fused_two_inputs[sim-shape0-24-2-dtype1]", OPS + "test_groupnorm_silu[sim-24-16-dtype1]"],
     "pyramid.hip": [OPS + "test_pyramids_equal_their_chains[sim-dtype1]"],
