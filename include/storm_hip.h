@@ -108,7 +108,8 @@ typedef struct storm_conv_args {
     int Cout;                   /* valid output channels (<= outC); the rest are written 0+skip */
     long long out_bstride;
     const float* bias;          /* [Cout] or NULL                                         */
-    const float* tbias;         /* [B][tbias_stride] per-batch per-channel bias or NULL   */
+    const float* tbias;         /* [B][tbias_stride] per-batch per-channel bias or NULL; rows are read 16 bytes at a time:
+                                 * tbias 16-byte aligned, tbias_stride a multiple of 4 (bias: 16-byte aligned)           */
     int tbias_stride;
     const void* skip;           /* NHWC like out (same dtype as activations) or NULL      */
     long long skip_bstride;
