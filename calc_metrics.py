@@ -2,7 +2,7 @@
 """Score a directory of enhanced files against the clean and noisy ones - the reference's calc_metrics step on the device:
 
     python calc_metrics.py --clean_dir clean/ --noisy_dir noisy/ --enhanced_dir out/ [--batch 16] [--resample] [--stoi]
-                           [--align [--max-lag SECONDS]] [--hp-filter [HZ]] [--sdr [TAPS]] [--bss [TAPS]]
+                           [--align [--max-lag SECONDS]] [--hp-filter [HZ]] [--sdr [TAPS]] [--bss [TAPS]] [--lpc]
 
 Files are matched by basename (every *.wav of --enhanced_dir needs its clean and noisy namesake).  Each triple is trimmed to its
 shortest member, the triples are bucketed by frame count and scored as ragged micro-batches (storm_amd.util.inference.score_batch:
@@ -11,7 +11,7 @@ SI-SDR / SI-SIR / SI-SAR, LSD and the input SNR, util/other.py:16-44, 96-100); P
 
     _results.csv       Filename,Length,iSNR,si_sdr,si_sir,si_sar,lsd[,pesq,estoi] - one line per file, Length in samples at 16 kHz
                        (--stoi: ...,lsd[,pesq],stoi,estoi; --sdr: then sdr; --bss: then bss_sdr,bss_sir,bss_sar;
-                       --align: lag, always last)
+                       --lpc: then seg_snr,llr,cd; --align: lag, always last)
     _avg_results.txt   metric: mean ± std of each column (mean_std, NaNs dropped)
 
 A file's line does not depend on --batch nor on the other files.  --resample: files of other rates are resampled to 16 kHz on the
@@ -29,7 +29,12 @@ distortion (storm_bss_sdr_rows, defined in include/storm_hip.h; not compared wit
 --bss [TAPS]: the columns bss_sdr,bss_sir,bss_sar, BSS-eval with two sources: the enhanced file is allowed a filter of TAPS taps of the clean
 file AND one of the noise (noisy - clean), solved jointly; bss_sir is the noise that is left, bss_sar what neither explains, where si_sir /
 si_sar book any filter as interference and artefacts (storm_bss_eval_rows, defined in include/storm_hip.h; BSS-eval's split, not compared
-with mir_eval).  bss_sdr is the column sdr of --sdr at the same TAPS.  Computed on what --hp-filter and --align leave."""
+with mir_eval).  bss_sdr is the column sdr of --sdr at the same TAPS.  Computed on what --hp-filter and --align leave.
+--lpc: the columns seg_snr,llr,cd, the frame-based measures of the enhanced file against the clean one: segmental SNR (dB, frames clamped to
+[-10, 35]), log-likelihood ratio (frames clamped to [0, 2]) and LPC cepstral distance (dB, frames clamped to [0, 10]) over 30 ms frames at
+3/4 overlap with LPC order 16, the last two as means of the 95 % smallest frame values (storm_lpc_measures_rows, defined in
+include/storm_hip.h and checked against a restatement of that text, not against pysepm).  Computed on what --hp-filter and --align leave; a
+file shorter than 37.5 ms prints nan, and mean_std leaves a nan out of the averages."""
 import glob
 import os
 from argparse import ArgumentParser
@@ -42,6 +47,7 @@ from enhancement import read_wav
 SR = 16000
 COLUMNS = ("iSNR", "si_sdr", "si_sir", "si_sar", "lsd")
 BSS_COLUMNS = ("bss_sdr", "bss_sir", "bss_sar")
+LPC_COLUMNS = ("seg_snr", "llr", "cd")
 KEYS = {"iSNR": "isnr", "si_sdr": "si_sdr", "si_sir": "si_sir", "si_sar": "si_sar", "lsd": "lsd"}
 
 
@@ -61,6 +67,8 @@ def main():
                    help="append the column sdr: the BSS-eval SDR with a filter of TAPS taps (512 when no value is given), on the device")
     p.add_argument("--bss", type=int, nargs="?", const=512, default=None, metavar="TAPS",
                    help="append the columns bss_sdr,bss_sir,bss_sar: BSS-eval against clean and noise with filters of TAPS taps (512 when no value is given), on the device")
+    p.add_argument("--lpc", action="store_true",
+                   help="append the columns seg_snr,llr,cd: segmental SNR, log-likelihood ratio and LPC cepstral distance, on the device")
     args = p.parse_args()
     if args.sdr is not None and not 1 <= args.sdr <= 512:
         p.error("--sdr TAPS: 1 to 512")
@@ -88,7 +96,7 @@ def main():
         n = min(x.shape[0], y.shape[0], e.shape[0])
         triples.append((x[:n], y[:n], e[:n]))
     lengths = [t[0].shape[0] for t in triples]
-    device_columns = COLUMNS + (("stoi", "estoi") if args.stoi else ()) + (("sdr",) if args.sdr is not None else ()) + (BSS_COLUMNS if args.bss is not None else ()) + (("lag",) if args.align else ())
+    device_columns = COLUMNS + (("stoi", "estoi") if args.stoi else ()) + (("sdr",) if args.sdr is not None else ()) + (BSS_COLUMNS if args.bss is not None else ()) + (LPC_COLUMNS if args.lpc else ()) + (("lag",) if args.align else ())
     values = {c: [None] * len(names) for c in device_columns}
     for ids in D.bucket_by_frames(lengths, args.batch):
         lens = [lengths[i] for i in ids]
@@ -105,6 +113,8 @@ def main():
             kw.update(sdr=True, sdr_taps=args.sdr)
         if args.bss is not None:
             kw.update(bss=True, bss_taps=args.bss)
+        if args.lpc:
+            kw.update(lpc=True, fs=SR)
         scores = {k: v.cpu() for k, v in score_batch(rows[0], rows[1], rows[2], lengths=lens, **kw).items()}
         for k, i in enumerate(ids):
             for c in device_columns:
@@ -124,6 +134,8 @@ def main():
         columns += ["sdr"]
     if args.bss is not None:
         columns += list(BSS_COLUMNS)
+    if args.lpc:
+        columns += list(LPC_COLUMNS)
     if args.align:
         columns += ["lag"]
 

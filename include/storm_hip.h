@@ -587,6 +587,55 @@ int storm_stoi_rows(const float* x, const float* y, double* out, void* scratch, 
                     long long stride_x, long long stride_y, const int* row_len, storm_stream_t st);
 
 /* ------------------------------------------------------------------------------------------
+ * Frame-based measures of enhanced audio: segmental SNR, log-likelihood ratio (LLR) and LPC cepstral distance (CD) per row - the family of
+ * Quackenbush, Barnwell, Clements 1988 as the evaluation code of Hu, Loizou 2008 and the REVERB challenge use it.  The reference has no
+ * such metric, so THIS TEXT is the specification; the numbers were checked against a float64 restatement of it (tests/lpc_cases.py), not
+ * against pysepm.  Inputs: x (clean) and y (processed) fp32, the row's first `len` samples of each, at fs Hz; after a sample is read all
+ * arithmetic is fp64.
+ * Constants: W = (30 fs + 500) / 1000 and H = W / 4 in integer division (16 kHz: 480, 120; 8 kHz: 240, 60; 44.1 kHz: 1323, 330);
+ *   P = 16 for fs >= 10000, else 10; EPS = 2^-52.  Refused: fs with W <= 2 P or W > 2048.
+ *  1. Frames: M = (len - W) / H by floor division for len >= W, else 0; frame m covers samples m H .. m H + W - 1.  This is the count of the
+ *     published MATLAB / pysepm code as recalled here, ONE SHORT of every full frame of the row (the frame that ends at or just before the
+ *     last sample is not taken); it is kept so that numbers compare with the literature.
+ *  2. Window: w[n] = 0.5 (1 - cos(2 pi (n + 1) / (W + 1))), n = 0 .. W - 1; c = w x_frame, p = w y_frame.
+ *  3. Segmental SNR of a frame: 10 log10(sum c^2 / (sum (c - p)^2 + EPS) + EPS) clamped to [-10, 35] dB; defined for every frame (a silent
+ *     clean frame gives -10).
+ *  4. LPC: r[k] = sum_n v[n] v[n + k], k = 0 .. P, for v = c and v = p.  A frame with r_c[0] <= 0 or r_p[0] <= 0 is VOID for LLR and CD (not
+ *     for the segmental SNR).  Levinson-Durbin: a = (1, a_1 .. a_P), E_0 = r[0]; at order i = 1 .. P
+ *       k_i = -(r[i] + sum_{j=1}^{i-1} a_j r[i-j]) / E   (j ascending, starting from r[i]),
+ *       a_j += k_i a_{i-j} for all j < i at once,  a_i = k_i,  E *= 1 - k_i^2;
+ *     the recursion stops before an order whose incoming E <= 2^-40 r[0], the remaining coefficients are 0.
+ *  5. LLR of a frame: ln((a_p' R_c a_p) / (a_c' R_c a_c)), R_c = Toeplitz(r_c[0 .. P]), clamped to [0, 2].  A quadratic form is
+ *     sum_i a_i (sum_j R_c[i][j] a_j), i and j ascending.
+ *  6. CD of a frame: the cepstrum of 1 / A(z), c_1 = -a_1, c_n = -a_n - sum_{k=1}^{n-1} (k / n) c_k a_{n-k} for n <= P (k ascending);
+ *     CD = (10 / ln 10) sqrt(2 sum_{n=1}^{P} (c_c[n] - c_p[n])^2) clamped to [0, 10] dB.
+ *  7. Row values: the segmental SNR is the mean over the M frames (NaN for M = 0).  LLR and CD are each the mean of the
+ *     n_keep = max(1, floor(0.95 M' + 0.5)) SMALLEST values among the M' frames that are not void - the published 95 % trim, n_keep in
+ *     integer arithmetic as max(1, (19 M' + 10) / 20) - and NaN for M' = 0.  A clamp leaves a NaN a NaN; a frame whose LLR is NaN counts as void.
+ *  Order of every sum (a row's numbers are the same bits alone, in any batch, at any batch width, row stride and position; no atomics):
+ *   inside a frame, lane l of a wave of 64 adds the terms n = l, l + 64, ... in ascending order as fused multiply-adds from +0, then the 64
+ *   lane sums are added in a butterfly (l with l ^ 32, ^ 16, ... ^ 1);  over a row, thread t of 256 adds the frames t, t + 256, ... in
+ *   ascending order, the butterfly adds each wave's 64 sums, and the four wave sums are added in wave order.  The trimmed mean is
+ *   (sum of the values below T in that order + (n_keep - their count) T) / n_keep, T the n_keep-th smallest value.  The recursions and the
+ *   quadratic forms of steps 4 - 6 run in the order written there, every product and sum rounded on its own (not fused).
+ *   One workgroup takes STORM_LPC_TILE consecutive frames of one row: the cut depends on the frame index only.
+ *
+ * storm_lpc_window (host): w of step 2 for fs in fp64 into the CALLER's host memory of `capacity` doubles; returns W, or < 0 when refused
+ *   (fs, null pointer, capacity < W).  The caller copies the table to the device.
+ * storm_lpc_measures_rows: x, y fp32 [B][L] at fs (row strides in floats), window = that table on the device -> out fp64 [B][3] =
+ *   (segmental SNR, LLR, CD).  frames_out (optional): fp64 [B][M(L)][3], the per-frame values of steps 3, 5, 6; NaN past a row's own M and,
+ *   in LLR and CD, for void frames.  row_len (optional, device int32 [B]): row b is its first row_len[b] samples (clipped to L), the rest
+ *   is never read.
+ *   scratch: at least storm_lpc_measures_scratch_bytes(B, L, fs) bytes of device memory (0: refused arguments), 8-byte aligned; after the
+ *   call it begins with int32 [B][2] = (M, M') of every row.  The library allocates nothing. */
+#define STORM_LPC_TILE 8
+int storm_lpc_window(int fs, double* w, long long capacity);
+long long storm_lpc_measures_scratch_bytes(int B, long long L, int fs);
+int storm_lpc_measures_rows(const float* x, const float* y, const double* window, double* out, double* frames_out, void* scratch,
+                            long long scratch_bytes, int B, long long L, long long stride_x, long long stride_y, const int* row_len, int fs,
+                            storm_stream_t st);
+
+/* ------------------------------------------------------------------------------------------
  * Long recordings: a recording longer than one window of W samples is enhanced as n overlapping windows (overlap V, 1 <= V <= W / 2, hop
  * H = W - V, window k starts at k H, n = ceil((L - V) / H)) and stitched back.  Output sample m < L of a recording:
  *   k = min(m / H, n - 1), j = m - k H, cur = window_k[j];

@@ -28,6 +28,7 @@ XCORR_PARTIAL_BYTES = 16         # include/storm_hip.h: STORM_XCORR_PARTIAL_BYTE
 SOS_MAX_SECTIONS = 16            # include/storm_hip.h: STORM_SOS_MAX_SECTIONS
 BSS_MAX_TAPS = 512               # include/storm_hip.h: STORM_BSS_MAX_TAPS, the longest filter storm_bss_sdr_rows allows the estimate
 BSS_PIECE = 16384                # include/storm_hip.h: STORM_BSS_PIECE, the samples one workgroup of storm_bss_sdr_rows correlates
+LPC_TILE = 8                     # include/storm_hip.h: STORM_LPC_TILE, the consecutive frames one workgroup of storm_lpc_measures_rows takes
 RAMP_KINDS = {"hann": 0, "linear": 1}        # include/storm_hip.h: STORM_RAMP_HANN, STORM_RAMP_LINEAR
 
 
@@ -162,6 +163,9 @@ _SIGNATURES = {
     "storm_resample_poly_taps": ([_vp, _vp, _vp, _i, _ll, _ll, _ll, _ll, _vp, _i, _i, _i, _vp], C.c_int),
     "storm_stoi_scratch_bytes": ([_i, _ll], C.c_longlong),
     "storm_stoi_rows": ([_vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _vp, _vp], C.c_int),
+    "storm_lpc_window": ([_i, _vp, _ll], C.c_int),
+    "storm_lpc_measures_scratch_bytes": ([_i, _ll, _i], C.c_longlong),
+    "storm_lpc_measures_rows": ([_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _vp, _i, _vp], C.c_int),
     "storm_crossfade_ramp": ([_i, _i, _vp], C.c_int),
     "storm_crossfade_rows": ([_vp, _i, _ll, _vp, _i, _ll, _ll, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp], C.c_int),
     "storm_xcorr_num_partials": ([_ll, _ll, _i], C.c_int),

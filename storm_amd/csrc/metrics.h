@@ -4,6 +4,8 @@
 // one workgroup sums one piece in fp64 in an order that depends on the position inside the piece only, writes its partial to caller-owned
 // scratch, and a second kernel adds a row's partials in index order and forms the numbers.  No atomics; the cut depends on the sample /
 // (bin, frame) index only, so a row's results are the same bits at any batch size, batch width, row stride and position in the batch.
+// The frame-based measures (segmental SNR, log-likelihood ratio, LPC cepstral distance; the reference has none of them) follow below the
+// two: frames cut at fixed positions, per-frame numbers in caller-owned scratch, a row kernel with sums in index order.
 // Included by spectral.hip alone (kernels and entry points live in that translation unit).
 #pragma once
 #include "common.h"
@@ -156,6 +158,325 @@ __global__ void lsd_finish_kernel(const double* __restrict__ part, double* __res
     out[b] = sqrt(sum / ((double)F * (double)frames));
 }
 
+// ---- frame-based measures: segmental SNR, log-likelihood ratio, LPC cepstral distance (definition in include/storm_hip.h) -----------------
+// Three launches for the whole batch:
+//   lpc_frames_kernel   one workgroup of four waves per LPC_TILE consecutive frames of one row (the cut depends on the frame index only).
+//                       The strip of both signals that the tile's frames share (they overlap by 3/4) and the window are staged in LDS once;
+//                       wave v owns frames v, v + 4, ... of the tile: it writes the windowed frame into its own LDS buffer, lanes stride the
+//                       samples, and the 17 lags and the error energy are reduced with wave_sum_d - first the clean frame, then the processed
+//                       one through the same buffer.  It writes the segmental SNR and the 2 x 17 lags of every frame to the caller's scratch.
+//   lpc_model_kernel    one LANE per frame: Levinson-Durbin, the cepstrum recursion and the quadratic form of both signals in registers, then
+//                       LLR and CD (NaN for a void frame).  The recursions are serial chains of dependent fp64 operations: as the tail of the
+//                       frames kernel they kept 16 lanes of a workgroup busy and the other 240 waiting (17.8 us per tile and CU on the
+//                       MI355X); one lane per frame fills whole waves with them.
+//   lpc_rows_kernel     one workgroup per row: the mean of the segmental SNR; the number of frames that are not void; for LLR and for CD the
+//                       n_keep-th smallest value T by a bisection over the fp64 bit pattern (63 counting passes, both measures at once - a
+//                       non-negative double orders as its bits), then (sum of the values below T + (n_keep - their count) T) / n_keep.
+// Every sum: thread t adds its elements t, t + threads, ... in ascending order, wave_sum_d, the four waves' sums in wave order.  No atomics.
+constexpr int LPC_TILE = STORM_LPC_TILE;                               // frames per workgroup
+constexpr int LPC_MAX_W = 2048, LPC_MAX_P = 16, LPC_LAGS = LPC_MAX_P + 1;
+constexpr int LPC_FPW = LPC_TILE / (METRICS_THREADS / 64);             // frames per wave
+constexpr int LPC_KEEP = 32;                                           // frames per thread that lpc_rows_kernel keeps in registers
+constexpr double LPC_EPS = 2.220446049250313e-16;                      // 2^-52
+constexpr double LPC_STOP = 9.094947017729282e-13;                     // 2^-40: Levinson-Durbin stops before an order with E <= 2^-40 r[0]
+constexpr double LPC_PI = 3.14159265358979323846;
+constexpr double LPC_DB = 4.342944819032518;                           // 10 / ln 10
+
+// W, H, P of a sample rate; false = refused (2 P < W <= 2048)
+__host__ __device__ inline bool lpc_shape(int fs, int& W, int& H, int& P) {
+    if (fs < 1) return false;
+    const long long w = (30ll * fs + 500) / 1000;
+    P = fs >= 10000 ? 16 : 10;
+    if (w <= 2 * P || w > LPC_MAX_W) return false;
+    W = (int)w; H = W / 4;
+    return true;
+}
+__host__ __device__ inline long long lpc_frames(long long len, int W, int H) { return len >= W ? (len - W) / H : 0; }
+__device__ __forceinline__ long long lpc_row_len(const int* row_len, int b, long long L) {
+    long long len = row_len ? (long long)row_len[b] : L;
+    return len > L ? L : len;                                          // (a device-side length the host never saw must still not read outside the row)
+}
+// v clamped to [lo, hi]; a NaN stays NaN, -0 becomes +0
+__device__ __forceinline__ double lpc_clamp(double v, double lo, double hi) { return (v < lo ? lo : (v > hi ? hi : v)) + 0.0; }
+
+// the dynamic LDS of lpc_frames_kernel, doubles first: win[W], buf[4][W + 16]; then the two strips
+__host__ __device__ inline int lpc_strip(int W, int H) { return (LPC_TILE - 1) * H + W; }
+__host__ __device__ inline int lpc_lds_doubles(int W) { return W + (METRICS_THREADS / 64) * (W + LPC_MAX_P); }
+inline int lpc_lds_bytes(int W, int H) { return lpc_lds_doubles(W) * (int)sizeof(double) + 2 * lpc_strip(W, H) * (int)sizeof(float); }
+
+// the 17 lags of the windowed frame in buf[0 .. W) (buf[W .. W + 16) is zero): lane l adds n = l, l + 64, ... ascending, then wave_sum_d.
+// Lags past P are computed and not used.
+__device__ __forceinline__ void lpc_lags(const double* __restrict__ buf, int W, int lane, double (&r)[LPC_LAGS]) {
+#pragma unroll
+    for (int k = 0; k < LPC_LAGS; ++k) r[k] = 0.0;
+    for (int n = lane; n < W; n += 64) {
+        const double v = buf[n];
+#pragma unroll
+        for (int k = 0; k < LPC_LAGS; ++k) r[k] = fma(v, buf[n + k], r[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < LPC_LAGS; ++k) r[k] = wave_sum_d(r[k]);
+}
+
+// One signal of one frame, in registers (every loop is unrolled: all indices are compile-time): Levinson-Durbin on the lags r, the cepstrum
+// of 1 / A(z) and the quadratic form a' Toeplitz(rc) a (rows ascending, inside a row the columns ascending).  out[0] = the form,
+// out[1 .. P] = the cepstrum.
+template <int P>
+__device__ __forceinline__ void lpc_model(const double* rl, const double* rcl, double (&out)[LPC_LAGS]) {
+    double r[P + 1], a[P + 1], c[P + 1];
+#pragma unroll
+    for (int j = 0; j <= P; ++j) { r[j] = rl[j]; a[j] = 0.0; c[j] = 0.0; }
+    a[0] = 1.0;
+    if (r[0] > 0.0) {                                                  // (a void frame: nothing reads its numbers)
+        double E = r[0];
+        bool go = true;
+#pragma unroll
+        for (int i = 1; i <= P; ++i) {
+            go = go && !(E <= LPC_STOP * r[0]);                        // stops before an order with E <= 2^-40 r[0]: the rest stays 0
+            if (go) {
+                double acc = r[i];
+#pragma unroll
+                for (int j = 1; j < i; ++j) acc += a[j] * r[i - j];
+                const double k = -acc / E;
+#pragma unroll
+                for (int j = 1; 2 * j <= i; ++j) {                     // a_j += k a_{i-j} for all j < i at once, in pairs (j, i - j)
+                    const double lo = a[j], hi = a[i - j];
+                    a[j] = lo + k * hi;
+                    if (j != i - j) a[i - j] = hi + k * lo;
+                }
+                a[i] = k;
+                E *= 1.0 - k * k;
+            }
+        }
+#pragma unroll
+        for (int n = 1; n <= P; ++n) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 1; k < n; ++k) acc += ((double)k / (double)n) * c[k] * a[n - k];
+            c[n] = -a[n] - acc;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j <= P; ++j) r[j] = rcl[j];
+    double form = 0.0;
+#pragma unroll
+    for (int i = 0; i <= P; ++i) {
+        double rowsum = 0.0;
+#pragma unroll
+        for (int j = 0; j <= P; ++j) rowsum += r[i > j ? i - j : j - i] * a[j];
+        form += a[i] * rowsum;
+    }
+    out[0] = form;
+#pragma unroll
+    for (int n = 1; n <= P; ++n) out[n] = c[n];
+}
+
+// fr[b][m][0] = the segmental SNR of frame m, lags[b][m][s][k] = r[k] of its clean (s = 0) and processed (s = 1) windowed frame
+__global__ void __launch_bounds__(METRICS_THREADS)
+lpc_frames_kernel(const float* __restrict__ x, const float* __restrict__ y, const double* __restrict__ window, double* __restrict__ fr,
+                  double* __restrict__ lags, long long L, long long stride_x, long long stride_y, const int* __restrict__ row_len,
+                  long long Mmax, int W, int H) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int S = lpc_strip(W, H), WB = W + LPC_MAX_P;
+    double* const win = reinterpret_cast<double*>(smem);
+    double* const bufs = win + W;
+    float* const xs = reinterpret_cast<float*>(bufs + (METRICS_THREADS / 64) * WB);
+    float* const ys = xs + S;
+    const int b = blockIdx.y, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const long long m0 = (long long)blockIdx.x * LPC_TILE;
+    const long long M = lpc_frames(lpc_row_len(row_len, b, L), W, H);
+    if (m0 >= M) return;                                               // (uniform in the workgroup) a tile past the row's frames
+    const int live = (int)(M - m0 < LPC_TILE ? M - m0 : LPC_TILE);     // frames of this tile; its samples end at (m0 + live - 1) H + W <= len
+    {
+        const float* px = x + (long long)b * stride_x + m0 * H;
+        const float* py = y + (long long)b * stride_y + m0 * H;
+        const int ns = (live - 1) * H + W;
+        for (int i = t; i < ns; i += METRICS_THREADS) { xs[i] = px[i]; ys[i] = py[i]; }
+        for (int i = t; i < W; i += METRICS_THREADS) win[i] = window[i];
+        if (lane < LPC_MAX_P) bufs[wv * WB + W + lane] = 0.0;
+    }
+    __syncthreads();
+    double* const buf = bufs + wv * WB;
+    for (int i = 0; i < LPC_FPW; ++i) {                                // (every wave walks the barriers; a wave without a frame only waits)
+        const int f = wv + i * (METRICS_THREADS / 64);
+        const bool on = f < live;
+        const long long m = (long long)b * Mmax + m0 + f;
+        double r[LPC_LAGS];
+        double ed = 0.0;
+        if (on) {
+            const float* fx = xs + f * H;
+            const float* fy = ys + f * H;
+            for (int n = lane; n < W; n += 64) {
+                const double c = win[n] * (double)fx[n], p = win[n] * (double)fy[n], d = c - p;
+                ed = fma(d, d, ed);
+                buf[n] = c;
+            }
+        }
+        __syncthreads();
+        if (on) {
+            lpc_lags(buf, W, lane, r);
+            ed = wave_sum_d(ed);
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < LPC_LAGS; ++k) lags[(m * 2 + 0) * LPC_LAGS + k] = r[k];
+                fr[m * 3] = lpc_clamp(10.0 * log10(r[0] / (ed + LPC_EPS) + LPC_EPS), -10.0, 35.0);
+            }
+        }
+        __syncthreads();                                               // (the clean frame is read: the buffer takes the processed one)
+        if (on) {
+            const float* fy = ys + f * H;
+            for (int n = lane; n < W; n += 64) buf[n] = win[n] * (double)fy[n];
+        }
+        __syncthreads();
+        if (on) {
+            lpc_lags(buf, W, lane, r);
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < LPC_LAGS; ++k) lags[(m * 2 + 1) * LPC_LAGS + k] = r[k];
+            }
+        }
+        __syncthreads();                                               // (the next frame overwrites the buffer)
+    }
+}
+
+// LLR and CD of a frame from its two rows of lags
+template <int P>
+__device__ __forceinline__ void lpc_frame_numbers(const double* r, double& llr, double& cd) {
+    double oc[LPC_LAGS], op[LPC_LAGS];                                 // [0]: a' R_c a, [1 .. P]: the cepstrum; clean, processed
+    lpc_model<P>(r, r, oc);
+    lpc_model<P>(r + LPC_LAGS, r, op);
+    double d2 = 0.0;
+#pragma unroll
+    for (int n = 1; n <= P; ++n) { const double d = oc[n] - op[n]; d2 += d * d; }
+    llr = lpc_clamp(log(op[0] / oc[0]), 0.0, 2.0);
+    cd = lpc_clamp(LPC_DB * sqrt(2.0 * d2), 0.0, 10.0);
+}
+
+// fr[b][m][1 .. 2] = (LLR, CD) of frame m, NaN for a void frame; frames_out (optional) gets the frame's three numbers, NaN past the row's own
+// frames.  One lane per frame.
+__global__ void __launch_bounds__(64)
+lpc_model_kernel(const double* __restrict__ lags, double* __restrict__ fr, double* __restrict__ frames_out, long long L,
+                 const int* __restrict__ row_len, long long Mmax, int W, int H, int P) {
+    const int b = blockIdx.y;
+    const long long f = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (f >= Mmax) return;
+    const long long M = lpc_frames(lpc_row_len(row_len, b, L), W, H);
+    const long long o = ((long long)b * Mmax + f) * 3;
+    const double nan = __builtin_bit_cast(double, 0x7ff8000000000000ull);
+    if (f >= M) {
+        if (frames_out) { frames_out[o] = nan; frames_out[o + 1] = nan; frames_out[o + 2] = nan; }
+        return;
+    }
+    const double* r = lags + ((long long)b * Mmax + f) * 2 * LPC_LAGS;
+    double llr = nan, cd = nan;
+    if (r[0] > 0.0 && r[LPC_LAGS] > 0.0) {
+        if (P == 16) lpc_frame_numbers<16>(r, llr, cd);
+        else lpc_frame_numbers<10>(r, llr, cd);
+    }
+    fr[o + 1] = llr; fr[o + 2] = cd;
+    if (frames_out) { frames_out[o] = fr[o]; frames_out[o + 1] = llr; frames_out[o + 2] = cd; }
+}
+
+// the workgroup's sum of one double / two counts per thread: wave sums, then the waves in order (every thread returns the same bits)
+__device__ __forceinline__ double lpc_block_sum(double v, double* red, int t) {
+    v = wave_sum_d(v);
+    __syncthreads();                                                   // (the previous use of red is read)
+    if ((t & 63) == 0) red[t >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+__device__ __forceinline__ void lpc_block_count2(int& a, int& c, int* red, int t) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); c += __shfl_xor(c, o, 64); }
+    __syncthreads();
+    if ((t & 63) == 0) { red[2 * (t >> 6)] = a; red[2 * (t >> 6) + 1] = c; }
+    __syncthreads();
+    a = red[0] + red[2] + red[4] + red[6];
+    c = red[1] + red[3] + red[5] + red[7];
+}
+
+// out[b] = (mean segmental SNR, trimmed mean LLR, trimmed mean CD), counts[b] = (M, M'): one workgroup per row
+__global__ void __launch_bounds__(METRICS_THREADS)
+lpc_rows_kernel(const double* __restrict__ fr, double* __restrict__ out, int* __restrict__ counts, long long L, const int* __restrict__ row_len,
+                long long Mmax, int W, int H) {
+    __shared__ double red[METRICS_THREADS / 64];
+    __shared__ int redi[2 * (METRICS_THREADS / 64)];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const long long M = lpc_frames(lpc_row_len(row_len, b, L), W, H);
+    const double* p = fr + (long long)b * Mmax * 3;
+    const double nan = __builtin_bit_cast(double, 0x7ff8000000000000ull);
+    double s = 0.0;
+    int nv = 0, unused = 0;
+    // the row's first LPC_KEEP x 256 frames (61 s at 16 kHz) stay in this thread's registers as bit patterns, all ones for a void frame or none:
+    // the counting passes below read only the frames past them from memory
+    unsigned long long k1[LPC_KEEP], k2[LPC_KEEP];
+#pragma unroll
+    for (int i = 0; i < LPC_KEEP; ++i) {
+        const long long m = t + (long long)i * METRICS_THREADS;
+        k1[i] = ~0ull; k2[i] = ~0ull;
+        if (m < M) {
+            const double v1 = p[3 * m + 1], v2 = p[3 * m + 2];
+            s += p[3 * m];
+            if (v1 == v1) { ++nv; k1[i] = __builtin_bit_cast(unsigned long long, v1); k2[i] = __builtin_bit_cast(unsigned long long, v2); }   // (a void frame's LLR is NaN)
+        }
+    }
+    for (long long m = t + (long long)LPC_KEEP * METRICS_THREADS; m < M; m += METRICS_THREADS) {
+        s += p[3 * m];
+        nv += p[3 * m + 1] == p[3 * m + 1] ? 1 : 0;
+    }
+    s = lpc_block_sum(s, red, t);
+    lpc_block_count2(nv, unused, redi, t);
+    const int keep = nv < 1 ? 0 : ((19 * (long long)nv + 10) / 20 < 1 ? 1 : (int)((19 * (long long)nv + 10) / 20));   // max(1, floor(0.95 M' + 0.5))
+    if (t == 0) {
+        counts[2 * b] = (int)M; counts[2 * b + 1] = nv;
+        out[3 * b] = M > 0 ? s / (double)M : nan;
+    }
+    if (keep == 0) {                                                   // (uniform in the workgroup)
+        if (t == 0) { out[3 * b + 1] = nan; out[3 * b + 2] = nan; }
+        return;
+    }
+    // T = the keep-th smallest bit pattern: bit by bit from the top, a bit is set when fewer than `keep` values lie below the pattern with it
+    unsigned long long T1 = 0ull, T2 = 0ull;
+    for (int bit = 62; bit >= 0; --bit) {
+        const unsigned long long c1 = T1 | (1ull << bit), c2 = T2 | (1ull << bit);
+        int n1 = 0, n2 = 0;
+#pragma unroll
+        for (int i = 0; i < LPC_KEEP; ++i) { n1 += k1[i] < c1 ? 1 : 0; n2 += k2[i] < c2 ? 1 : 0; }
+        for (long long m = t + (long long)LPC_KEEP * METRICS_THREADS; m < M; m += METRICS_THREADS) {
+            const double v1 = p[3 * m + 1], v2 = p[3 * m + 2];
+            if (v1 == v1) {
+                n1 += __builtin_bit_cast(unsigned long long, v1) < c1 ? 1 : 0;
+                n2 += __builtin_bit_cast(unsigned long long, v2) < c2 ? 1 : 0;
+            }
+        }
+        lpc_block_count2(n1, n2, redi, t);
+        if (n1 < keep) T1 = c1;
+        if (n2 < keep) T2 = c2;
+    }
+    const double t1 = __builtin_bit_cast(double, T1), t2 = __builtin_bit_cast(double, T2);
+    double s1 = 0.0, s2 = 0.0;
+    int n1 = 0, n2 = 0;
+#pragma unroll
+    for (int i = 0; i < LPC_KEEP; ++i) {
+        if (k1[i] < T1) { s1 += __builtin_bit_cast(double, k1[i]); ++n1; }
+        if (k2[i] < T2) { s2 += __builtin_bit_cast(double, k2[i]); ++n2; }
+    }
+    for (long long m = t + (long long)LPC_KEEP * METRICS_THREADS; m < M; m += METRICS_THREADS) {
+        const double v1 = p[3 * m + 1], v2 = p[3 * m + 2];
+        if (v1 == v1) {
+            if (v1 < t1) { s1 += v1; ++n1; }
+            if (v2 < t2) { s2 += v2; ++n2; }
+        }
+    }
+    s1 = lpc_block_sum(s1, red, t);
+    s2 = lpc_block_sum(s2, red, t);
+    lpc_block_count2(n1, n2, redi, t);
+    if (t == 0) {
+        out[3 * b + 1] = (s1 + (double)(keep - n1) * t1) / (double)keep;
+        out[3 * b + 2] = (s2 + (double)(keep - n2) * t2) / (double)keep;
+    }
+}
+
 }  // namespace storm
 
 extern "C" long long storm_energy_ratios_scratch_bytes(int B, long long L) {
@@ -200,6 +521,57 @@ extern "C" int storm_lsd_rows(const float* spec_hat, const float* spec, double* 
                        row_frames, eps);
     STORM_LAUNCH_CHECK();
     hipLaunchKernelGGL(lsd_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)st, (const double*)scratch, out, F, T, row_frames, nbt, nft, B);
+    STORM_LAUNCH_CHECK();
+    return STORM_OK;
+}
+
+extern "C" int storm_lpc_window(int fs, double* w, long long capacity) {
+    int W, H, P;
+    STORM_CHECK(storm::lpc_shape(fs, W, H, P), "storm_lpc_window: fs=%d (the window W = (30 fs + 500) / 1000 must satisfy 2 P < W <= %d)", fs, storm::LPC_MAX_W);
+    STORM_CHECK(w != nullptr, "storm_lpc_window: null pointer");
+    STORM_CHECK(capacity >= W, "storm_lpc_window: capacity %lld for a window of %d", capacity, W);
+    for (int n = 0; n < W; ++n) w[n] = 0.5 * (1.0 - cos(2.0 * storm::LPC_PI * (double)(n + 1) / (double)(W + 1)));
+    return W;
+}
+
+extern "C" long long storm_lpc_measures_scratch_bytes(int B, long long L, int fs) {
+    int W, H, P;
+    if (B <= 0 || B > 65535 || L <= 0 || L > (1ll << 30) || !storm::lpc_shape(fs, W, H, P)) return 0;
+    return (long long)B * 2 * (long long)sizeof(int) + (long long)B * storm::lpc_frames(L, W, H) * (3 + 2 * storm::LPC_LAGS) * (long long)sizeof(double);
+}
+
+extern "C" int storm_lpc_measures_rows(const float* x, const float* y, const double* window, double* out, double* frames_out, void* scratch,
+                                       long long scratch_bytes, int B, long long L, long long stride_x, long long stride_y, const int* row_len,
+                                       int fs, storm_stream_t st) {
+    using namespace storm;
+    int W, H, P;
+    STORM_CHECK(lpc_shape(fs, W, H, P), "storm_lpc_measures_rows: fs=%d (the window W = (30 fs + 500) / 1000 must satisfy 2 P < W <= %d)", fs, LPC_MAX_W);
+    STORM_CHECK(x && y && window && out && scratch, "storm_lpc_measures_rows: null pointer");
+    STORM_CHECK(B >= 1 && B <= 65535 && L >= 1 && L <= (1ll << 30), "storm_lpc_measures_rows: B=%d L=%lld", B, L);
+    STORM_CHECK(stride_x >= L && stride_y >= L, "storm_lpc_measures_rows: strides %lld %lld for rows of %lld", stride_x, stride_y, L);
+    STORM_CHECK(((uintptr_t)scratch & 7) == 0 && scratch_bytes >= storm_lpc_measures_scratch_bytes(B, L, fs),
+                "storm_lpc_measures_rows: scratch %p of %lld bytes, %lld needed (8-byte aligned)", scratch, scratch_bytes,
+                storm_lpc_measures_scratch_bytes(B, L, fs));
+    const long long Mmax = lpc_frames(L, W, H);
+    int* counts = (int*)scratch;
+    double* fr = (double*)((char*)scratch + (long long)B * 2 * sizeof(int));            // [B][Mmax][3]
+    double* lags = fr + (long long)B * Mmax * 3;                                          // [B][Mmax][2][17]
+    hipStream_t hs = (hipStream_t)st;
+    if (Mmax > 0) {
+        const int lds = lpc_lds_bytes(W, H);
+        static int lds_allowed = 64 * 1024;                            // (a window of more than ~1100 samples needs more than the default)
+        if (lds > lds_allowed) {
+            STORM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lpc_frames_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            lds_allowed = 160 * 1024;
+        }
+        hipLaunchKernelGGL(lpc_frames_kernel, dim3((unsigned)((Mmax + LPC_TILE - 1) / LPC_TILE), B), dim3(METRICS_THREADS), lds, hs, x, y, window, fr,
+                           lags, L, stride_x, stride_y, row_len, Mmax, W, H);
+        STORM_LAUNCH_CHECK();
+        hipLaunchKernelGGL(lpc_model_kernel, dim3((unsigned)((Mmax + 63) / 64), B), dim3(64), 0, hs, (const double*)lags, fr, frames_out, L, row_len,
+                           Mmax, W, H, P);
+        STORM_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(lpc_rows_kernel, dim3(B), dim3(METRICS_THREADS), 0, hs, (const double*)fr, out, counts, L, row_len, Mmax, W, H);
     STORM_LAUNCH_CHECK();
     return STORM_OK;
 }

@@ -19,7 +19,19 @@ def init(backend=None, single_rank_group=False):
         backend = backend or ("nccl" if torch.cuda.is_available() else "gloo")
         kw = dict(device_id=torch.device("cuda", local)) if backend == "nccl" else {}
         dist.init_process_group(backend, rank=rank, world_size=world, **kw)
+        if backend == "gloo":
+            # a rank that returns from its script without finish() takes the group's worker threads into interpreter shutdown still
+            # running: under load one of them is destroyed while joinable and the rank dies of `terminate called without an active
+            # exception` (SIGABRT) after all of its work is done.  Leave the group while the interpreter is whole; a no-op after finish().
+            import atexit
+            atexit.register(_leave_group)
     return rank, world, local
+
+
+def _leave_group():
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        dist.destroy_process_group()
 
 
 def parse_cpulist(text):

@@ -1041,6 +1041,66 @@ def stoi_rows(clean, estimate, lengths=None, fs=16000, counts=False):
     return (out, ws[:4 * B].reshape(B, 4)[:, :3].clone()) if counts else out
 
 
+# ---------------------------------------------------------------- frame-based measures ----
+LPC_TILE = L.LPC_TILE                    # consecutive frames per workgroup of storm_lpc_measures_rows (tests place frame counts around it)
+_lpc_windows = {}
+
+
+def lpc_shape(fs):
+    """(W, H, P) of include/storm_hip.h (storm_lpc_measures_rows) for a sample rate: window, hop and LPC order"""
+    fs = int(fs)
+    W = (30 * fs + 500) // 1000
+    return W, W // 4, 16 if fs >= 10000 else 10
+
+
+def _lpc_window(fs, device):
+    """the analysis window of the frame-based measures at fs, fp64 [W] on `device`: written by the library (storm_lpc_window), fetched once
+    per rate and device"""
+    key = (fs, str(device))
+    if key not in _lpc_windows:
+        host = torch.empty((max(lpc_shape(fs)[0], 1),), dtype=torch.float64)
+        n = L.lib().storm_lpc_window(fs, host.data_ptr(), host.numel())
+        if n < 0:
+            L.check(n, "storm_lpc_window")
+        _lpc_windows[key] = host[:n].to(device)
+    return _lpc_windows[key]
+
+
+def lpc_window(fs, device="cpu"):
+    """The window of the frame-based measures at `fs` as the kernel reads it: fp64 [W], w[n] = 0.5 (1 - cos(2 pi (n + 1) / (W + 1)))
+    (include/storm_hip.h: storm_lpc_window).  A copy: the cached table stays as the library wrote it."""
+    return _lpc_window(int(fs), torch.device(device)).clone()
+
+
+def lpc_measures_rows(x, y, lengths=None, fs=16000, frames=False, counts=False):
+    """fp64 [B, 3] = (segmental SNR in dB, log-likelihood ratio, LPC cepstral distance in dB) per row of the clean batch x and the processed
+    batch y, fp32 [B, L] at `fs` (rows may be strided views): the definition of include/storm_hip.h (storm_lpc_measures_rows).  A row with
+    fewer than W + H samples has no frame: three NaN; a row whose frames are all void (a silent signal) has NaN for LLR and CD.
+    lengths: per-row sample counts of a ragged batch (the rest of a row is not read).  A row's numbers do not depend on the batch it is in.
+    frames=True: also fp64 [B, M(L), 3], the per-frame values (NaN past a row's own frames and, in LLR and CD, for void frames).
+    counts=True: also int32 [B, 2] = the row's frames M and those that are not void M'.  Returned in this order: rows, frames, counts."""
+    for name, v in (("x", x), ("y", y)):
+        if v.dim() != 2 or v.dtype != torch.float32 or v.shape != x.shape:
+            raise ValueError(f"lpc_measures_rows: {name} is {v.dtype} {tuple(v.shape)}, expected float32 [B, L] = {tuple(x.shape)}")
+    B, Lw = x.shape
+    if B < 1 or Lw < 1:
+        raise ValueError(f"lpc_measures_rows: empty batch {tuple(x.shape)}")
+    _metric_lengths("lpc_measures_rows", lengths, B, Lw, "lengths")
+    fs = int(fs)
+    win = _lpc_window(fs, x.device)
+    W, H, _ = lpc_shape(fs)
+    rows = [v if v.stride(1) == 1 else v.contiguous() for v in (x, y)]
+    strides = [v.stride(0) if B > 1 else Lw for v in rows]       # (a one-row tensor's row stride is whatever its producer left there)
+    out = _alloc((B, 3), torch.float64, x)
+    per = _alloc((B, (Lw - W) // H if Lw >= W else 0, 3), torch.float64, x) if frames else None
+    ws = torch.empty((L.lib().storm_lpc_measures_scratch_bytes(B, Lw, fs) // 4,), dtype=torch.int32, device=x.device)
+    rl = _row_len(lengths, x)
+    L.check(L.lib().storm_lpc_measures_rows(L.ptr_rows(rows[0]), L.ptr_rows(rows[1]), L.ptr(win), L.ptr(out), L.ptr(per), L.ptr(ws),
+                                            4 * ws.numel(), B, Lw, strides[0], strides[1], L.ptr(rl), fs, L.stream()), "storm_lpc_measures_rows")
+    res = (out,) + ((per,) if frames else ()) + ((ws[:2 * B].reshape(B, 2).clone(),) if counts else ())
+    return res if len(res) > 1 else out
+
+
 # ---------------------------------------------------------------- misaligned audio --------
 XCORR_TILE = L.XCORR_TILE                # consecutive lags per workgroup of storm_xcorr_lag_rows (tests place delays around its multiples)
 SOS_MAX_SECTIONS = L.SOS_MAX_SECTIONS

@@ -32,10 +32,11 @@ def _optional(name, attr):
 
 
 METRIC_KEYS = ("si_sdr", "si_sir", "si_sar", "lsd", "isnr")
+LPC_KEYS = ("seg_snr", "llr", "cd")          # score_batch(lpc=True)
 
 
 def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, align=False, max_lag=None, hp=None, sdr=False, sdr_taps=512, bss=False,
-                bss_taps=512):
+                bss_taps=512, lpc=False):
     """The calc_metrics numbers of one micro-batch of device waveforms [B, L]: a dict of fp64 [B] tensors si_sdr / si_sir / si_sar
     (energy_ratios(estimate, clean, noisy - clean), util/other.py:35-44), lsd (estimate against clean, :16-19) and isnr (snr_dB(clean,
     noisy - clean), :96-100).  lengths: per-row sample counts of a ragged batch.  One energy launch pair, two STFTs and one LSD launch
@@ -48,7 +49,8 @@ def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, alig
     sdr=True adds the key sdr: the BSS-eval SDR of the estimate against clean with a filter of sdr_taps taps (ops.bss_sdr_rows), computed on
     what hp= and align= leave.  bss=True adds the keys bss_sdr, bss_sir, bss_sar: BSS-eval with two sources, target clean and noise noisy -
     clean, each allowed a filter of bss_taps taps, solved jointly (ops.bss_eval_rows; BSS-eval's split, not si_sir / si_sar), on the same
-    rows.  Without these keywords nothing changes."""
+    rows.  lpc=True adds the keys seg_snr, llr, cd: the frame-based measures of the estimate against clean at `fs` Hz (ops.lpc_measures_rows;
+    include/storm_hip.h has the definition), on the same rows.  Without these keywords nothing changes."""
     from .. import ops
     clean, noisy, estimate = clean.float(), noisy.float(), estimate.float()
     if hp is not None:
@@ -68,20 +70,24 @@ def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, alig
     if bss:
         d = ops.bss_eval_rows(clean, noisy - clean, estimate, lengths=lengths, flen=bss_taps)
         out["bss_sdr"], out["bss_sir"], out["bss_sar"] = d[:, 0], d[:, 1], d[:, 2]
+    if lpc:
+        d = ops.lpc_measures_rows(clean, estimate, lengths=lengths, fs=fs)
+        out["seg_snr"], out["llr"], out["cd"] = d[:, 0], d[:, 1], d[:, 2]
     if lag is not None:
         out["lag"] = lag
     return out
 
 
 def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminative=False, pairs=None, batch=16, noise_for=None,
-                   metrics=False, estoi=None, **enhance_kwargs):
+                   metrics=False, estoi=None, lpc=False, **enhance_kwargs):
     """Returns (pesq, si_sdr, estoi, [noisy, estimate, clean spectrograms] | None, [noisy, estimate, clean audio] | None),
     the reference's tuple.  `discriminative` is accepted for signature parity (the model class decides the path).
     noise_for(ids) -> noise_fn: injected sampler noise for the micro-batch of files `ids` (parity tests; production runs
     pass seed= and draw in-kernel).  metrics=True appends a sixth element: the means over the evaluated files of score_batch's
     numbers, {si_sdr, si_sir, si_sar, lsd, isnr} as floats, computed on the same micro-batches.
     estoi="device": the third element is the mean over the files of the device ESTOI (ops.stoi_rows at 16 kHz, one call per micro-batch),
-    whether or not pystoi imports, and the sixth element gains the means stoi and estoi; None: pystoi on the host, NaN without it."""
+    whether or not pystoi imports, and the sixth element gains the means stoi and estoi; None: pystoi on the host, NaN without it.
+    lpc=True (with metrics=True): the sixth element gains the means seg_snr, llr and cd of score_batch(lpc=True) at 16 kHz."""
     if estoi not in (None, "device"):
         raise ValueError(f"estoi={estoi!r}: None (pystoi on the host) or 'device'")
     model.eval()
@@ -94,7 +100,7 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
     dev = next(model.parameters()).device
     est = [None] * n
     sdr = torch.zeros(n, dtype=torch.float64)
-    scores = {k: torch.zeros(n, dtype=torch.float64) for k in METRIC_KEYS} if metrics else None
+    scores = {k: torch.zeros(n, dtype=torch.float64) for k in METRIC_KEYS + (LPC_KEYS if lpc else ())} if metrics else None
     intel = torch.zeros(n, 2, dtype=torch.float64) if estoi == "device" else None
     hop = model.data_module.hop_length
     batched = hasattr(model, "enhance_batch") and not discriminative
@@ -122,7 +128,7 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
                 sdr[i] = float(si_sdr_batch(x[k:k + 1, :lens[k]], x_hat[k:k + 1, :lens[k]]))
         if metrics:
             w = min(width, x_hat.shape[1])
-            for key, v in score_batch(x[:, :w], y[:, :w], x_hat[:, :w], lengths=[min(v, w) for v in lens]).items():
+            for key, v in score_batch(x[:, :w], y[:, :w], x_hat[:, :w], lengths=[min(v, w) for v in lens], **(dict(lpc=True) if lpc else {})).items():
                 scores[key][ids] = v.cpu()
         if intel is not None:
             from .. import ops

@@ -2,7 +2,7 @@
 pad_spec (:102-109), si_sdr / si_sdr_torch (:82-94), and the metrics of the calc_metrics step in batch form on the device:
 energy_ratios (:21-44), lsd (:16-19), snr_dB (:96-100); mean_std (:53-57) on the host; stoi: STOI / ESTOI on the device under the
 signature of pystoi.stoi, which the reference's evaluation calls; align (:153-157) and hp_filter (:76-80) on the device; sdr: the BSS-eval SDR with a short filter,
-which the reference does not have."""
+which the reference does not have; lpc_measures / seg_snr / llr / cepstral_distance: the frame-based measures, which it does not have either."""
 import warnings
 
 import numpy as np
@@ -164,6 +164,34 @@ def bss_eval(s, n, s_hat, flen=512, lengths=None):
     (sr, nr, er), one = _device_rows(s, n, s_hat)
     d = ops.bss_eval_rows(sr, nr, er, lengths=lengths, flen=flen)
     return tuple(float(d[0, k]) for k in range(3)) if one else (d[:, 0], d[:, 1], d[:, 2])
+
+
+def lpc_measures(s, s_hat, fs=16000, lengths=None):
+    """(seg_snr, llr, cd): segmental SNR in dB, log-likelihood ratio and LPC cepstral distance in dB of the estimate s_hat against the clean
+    s, in si_sdr's argument order, on the device - the frame-based measures of the enhancement and dereverberation literature (30 ms frames
+    at 3/4 overlap, LPC order 16, or 10 below 10 kHz; LLR and CD are means of the 95 % smallest frame values; storm_lpc_measures_rows;
+    include/storm_hip.h has the definition - the reference has no such metric, and nothing here was compared with pysepm).  s, s_hat: 1-D ->
+    three floats; [B, L] -> three fp64 tensors [B] on the device (lengths: per-row sample counts of a ragged batch).  A signal shorter than
+    37.5 ms gives NaN, a silent one NaN for llr and cd.  numpy arrays are moved to the current HIP device; fp32 is what the kernels read."""
+    from .. import ops
+    (sr, er), one = _device_rows(s, s_hat)
+    d = ops.lpc_measures_rows(sr, er, lengths=lengths, fs=fs)
+    return tuple(float(d[0, k]) for k in range(3)) if one else (d[:, 0], d[:, 1], d[:, 2])
+
+
+def seg_snr(s, s_hat, fs=16000, lengths=None):
+    """the segmental SNR of lpc_measures alone"""
+    return lpc_measures(s, s_hat, fs=fs, lengths=lengths)[0]
+
+
+def llr(s, s_hat, fs=16000, lengths=None):
+    """the log-likelihood ratio of lpc_measures alone"""
+    return lpc_measures(s, s_hat, fs=fs, lengths=lengths)[1]
+
+
+def cepstral_distance(s, s_hat, fs=16000, lengths=None):
+    """the LPC cepstral distance of lpc_measures alone"""
+    return lpc_measures(s, s_hat, fs=fs, lengths=lengths)[2]
 
 
 def mean_std(data):
