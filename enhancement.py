@@ -7,7 +7,8 @@
 Additions: --precision {fp32,bf16}, --batch (equal-length utterances per sampler call), --seed / --utterance-seed, --sampler ode with
 --ode-method {RK45,RK23,DOP853} / --ode-rtol / --ode-atol (what the reference hands to scipy.integrate.solve_ivp), --resample /
 --output-sr (files of other rates than 16 kHz, resampled on the device), --window / --overlap / --ramp / --skip-silent (long recordings as
-overlapping windows, pooled into full batches and cross-faded on the device: enhance_long) and multi-GPU sharding when launched with torchrun (one
+overlapping windows, pooled into full batches and cross-faded on the device: enhance_long), --draws / --combine / --spread-dir (several draws of the posterior
+per file, combined on the device: enhance_ensemble) and multi-GPU sharding when launched with torchrun (one
 process per GPU, files dealt by length; no collectives in the sampler).  WAV I/O uses scipy.io.wavfile (torchaudio is not required)."""
 import glob
 import hashlib
@@ -78,6 +79,12 @@ def main():
     p.add_argument("--overlap", type=float, default=0.512, help="with --window: seconds two neighbouring windows share (at most half a window)")
     p.add_argument("--ramp", choices=("hann", "linear"), default="hann", help="with --window: the cross-fade's weights over the overlap")
     p.add_argument("--skip-silent", action="store_true", help="with --window: windows whose every sample is zero are not sampled and come out as zeros")
+    p.add_argument("--draws", type=int, default=1, help="(extension) this many samples of the posterior per file, drawn as full batches and combined on the device "
+                   "(enhance_ensemble; draw k of a file uses the key ops.draw_key(file key, k)).  1: one draw per file, as upstream")
+    p.add_argument("--combine", choices=("mean", "mag_mean", "mag_median", "medoid"), default="mean", help="with --draws: the mean of the draws' linear spectrograms, the mean's "
+                   "phase with the mean / median of their magnitudes, or the draw closest to the mean")
+    p.add_argument("--spread-dir", type=str, default=None, help="with --draws: write every file's per-bin spread (the draws' standard deviation around their mean, fp32 "
+                   "[F, frames]) as <name>.npy into this directory")
     p.add_argument("--dist-world1",action="store_true", help="with ONE rank: form the RCCL process group anyway (dry run of the sharded path on one GPU)")
     args = p.parse_args()
     if args.seed is not None and args.utterance_seed is not None:
@@ -85,6 +92,14 @@ def main():
     ode_kw = {k: v for k, v in (("method", args.ode_method), ("rtol", args.ode_rtol), ("atol", args.ode_atol)) if v is not None}
     if ode_kw and args.sampler != "ode":
         raise SystemExit("--ode-method / --ode-rtol / --ode-atol: only with --sampler ode")
+    if args.draws < 1:
+        raise SystemExit(f"--draws {args.draws}: at least 1")
+    if args.draws > 1 and args.window is not None:
+        raise SystemExit("--draws: not together with --window (a long recording's windows are drawn once)")
+    if args.draws > 1 and args.mode == "denoiser-only":
+        raise SystemExit("--draws: the denoiser-only mode draws no noise, its one output is the only draw")
+    if args.draws == 1 and (args.spread_dir is not None or args.combine != "mean"):
+        raise SystemExit("--combine / --spread-dir: only with --draws K, K > 1")
     if args.sampler == "ode" and args.mode != "score-only":
         raise SystemExit("--sampler ode: score-only mode (the reference's StoRM ODE path drops the conditioning, model.py:671-691)")
 
@@ -159,6 +174,28 @@ def main():
         D.finish()
         return
     buckets = D.bucket_by_frames([lengths[i] for i in mine], args.batch)
+    if args.draws > 1:
+        # several draws per file: every micro-batch of files is ONE enhance_ensemble call - its (file, draw) pairs run as batches of --batch rows
+        # and are combined in one launch.  A file's key: its utterance key, --seed + its index, or drawn.
+        if args.spread_dir is not None:
+            os.makedirs(args.spread_dir, exist_ok=True)
+        dm = model.data_module
+        for batch in buckets:
+            ids = [mine[k] for k in batch]
+            lens = [lengths[i] for i in ids]
+            y = torch.zeros(len(ids), max(lens))
+            for k, i in enumerate(ids):
+                y[k, :lens[k]] = wavs[i][0]
+            file_keys = [keys[i] for i in ids] if keys is not None else (None if args.seed is None else [args.seed + i for i in ids])
+            res = model.enhance_ensemble(y, draws=args.draws, combine=args.combine, keys=file_keys, lengths=None if len(set(lens)) == 1 else lens,
+                                         batch=args.batch, return_spread=args.spread_dir is not None, **skw)
+            x_hat = res[0] if args.spread_dir is not None else res
+            for k, i in enumerate(ids):
+                write_enhanced(i, x_hat[k, :lens[k]])
+                if args.spread_dir is not None:
+                    frames = 1 + (lens[k] + 2 * (dm.n_fft // 2) - dm.n_fft) // dm.hop_length
+                    np.save(os.path.join(args.spread_dir, os.path.splitext(os.path.basename(files[i]))[0] + ".npy"), res[1][k, :, :frames].cpu().numpy())
+        buckets = []
     if args.mode in ("score-only", "storm") and args.group > 1 and len(buckets) > 1:
         # a ragged set of files: micro-batches of 2 - 3 rows each - their score evaluations share launches (storm_ncsnpp_forward_group)
         # (--group micro-batches in flight; one that finishes - an ODE micro-batch needs its own number of evaluations - is replaced by the next)

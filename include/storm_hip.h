@@ -659,6 +659,49 @@ int storm_crossfade_rows(const float* pool, int N, long long pool_stride, float*
                          const float* ramp, storm_stream_t st);
 
 /* ------------------------------------------------------------------------------------------
+ * Posterior ensembles: K draws of the sampler per utterance combined into one estimate, with a per-bin spread and per-row agreement
+ * numbers.  The reference has no ensemble, so THIS TEXT is the specification; the numbers were checked against a float64 restatement of
+ * it (tests/ensemble_cases.py).
+ * pool: complex64 [N][F][T] (T fastest, row stride pool_stride in complex elements), sampler outputs in the model's TRANSFORMED domain.
+ * draw_row: device int32 [B][K], the pool row of draw k of utterance b, every entry in [0, N), in any order (an entry outside the pool reads
+ *   as zeros: the host cannot see the table, the kernel must still not read outside the pool).
+ * frames (optional, device int32 [B]): the row's valid frame count; bins with t >= frames[b] are never read, out and spread are zeros there.
+ * 1 <= K <= STORM_ENSEMBLE_MAX_DRAWS.
+ * Per bin everything after the fp32 load is fp64, every product and sum rounded on its own (no contraction); |v|^2 of a complex v is
+ * v_re v_re + v_im v_im, |v| its square root:
+ *  1. Back-transform (data_module.py:188-193) of draw k, z_k = (re, im): r = sqrt(re re + im im); r == 0: x_k = 0.  Otherwise m_k = r / factor,
+ *     g = m_k for e == 1, m_k m_k for e == 0.5, else pow(m_k, 1 / e); x_k = (g (re / r), g (im / r)) and |x_k| = g (taken as g, not formed
+ *     again from x_k).  factor and e are the data module's fp32 values widened to fp64.
+ *  2. Mean: c = (sum_k x_k) / K, k ascending from +0, real and imaginary part each.
+ *  3. Combined value by mode - STORM_ENSEMBLE_MEAN: c;  STORM_ENSEMBLE_MAG_MEAN: a c / |c| with a = (sum_k |x_k|) / K (k ascending from +0);
+ *     STORM_ENSEMBLE_MAG_MEDIAN: a c / |c| with a the median of the |x_k| - the middle order statistic, for even K half the sum of the two
+ *     middle ones (0.5 (lower + upper)).  a c / |c| is (a (c_re / n), a (c_im / n)) with n = |c|; |c| == 0 gives 0 in the two magnitude
+ *     modes.  out: complex64 [B][F][T] in the LINEAR STFT domain, rounded to fp32 once.
+ *  4. Spread (optional, fp32 [B][F][T]): s = sqrt((sum_k |x_k - c|^2) / (K - 1)), k ascending from +0, as written (not E[x^2] - |c|^2);
+ *     0 for K = 1.
+ *  5. Row numbers: rows_out fp64 [B][2 + K] = (E, D, d_0 .. d_{K-1}) with E = sum over the valid bins of |c|^2, d_k = sum over the valid
+ *     bins of |x_k - c|^2 and D = (sum_k d_k) / K (k ascending from +0).  best[b] (int32) = the k with the smallest d_k, the lowest k on a
+ *     tie: the medoid draw.  10 log10(E / D) is the row's agreement in dB.
+ *  6. Order of the row sums (a row's bits are the same alone, in any batch, at any pool stride and under any permutation of pool rows; no
+ *     atomics): one workgroup takes STORM_ENSEMBLE_TILE consecutive bins of one row in i = f T + t order - the cut depends on the bin index
+ *     only.  The tile's bins form pairs (2 p, 2 p + 1); thread l of 256 adds the valid bins of its pairs p = l, l + 256, ... in ascending
+ *     bin order from +0 (lane-strided, ascending), the 64 lane sums of a wave are added in a butterfly (l with l ^ 32, ^ 16, ... ^ 1) and
+ *     the four wave sums in wave order - the orders of the frame-based measures above.  A second kernel adds a row's tile partials in tile
+ *     order from +0.
+ *
+ * storm_ensemble_combine_rows: out, and optionally spread, as above; scratch: at least storm_ensemble_scratch_bytes(B, F, T, K) bytes of
+ *   device memory (0: refused arguments), 8-byte aligned, the tile partials.  pool and out are 16-byte aligned.  Refused: null pointers (spread
+ *   and frames may be null), B, F, T, N < 1 (B <= 65535, F T < 2^31), K outside 1 .. STORM_ENSEMBLE_MAX_DRAWS, pool_stride < F T, a pool or
+ *   out that is not 16-byte aligned, scratch too small or misaligned, an unknown mode, factor or exponent <= 0.  The library allocates nothing. */
+#define STORM_ENSEMBLE_MAX_DRAWS 32
+#define STORM_ENSEMBLE_TILE 1024
+enum { STORM_ENSEMBLE_MEAN = 0, STORM_ENSEMBLE_MAG_MEAN = 1, STORM_ENSEMBLE_MAG_MEDIAN = 2 };
+long long storm_ensemble_scratch_bytes(int B, int F, int T, int K);
+int storm_ensemble_combine_rows(const float* pool, int N, long long pool_stride, const int* draw_row, float* out, float* spread,
+                                double* rows_out, int* best, void* scratch, long long scratch_bytes, int B, int K, int F, int T,
+                                const int* frames, float factor, float exponent, int mode, storm_stream_t st);
+
+/* ------------------------------------------------------------------------------------------
  * Misaligned audio (the reference's util/other.py: align :153-157, hp_filter :76-80).  Every scoring entry point above assumes that its
  * rows are sample-aligned; these find a delay, undo it and remove rumble without leaving the device.
  *

@@ -30,6 +30,9 @@ BSS_MAX_TAPS = 512               # include/storm_hip.h: STORM_BSS_MAX_TAPS, the 
 BSS_PIECE = 16384                # include/storm_hip.h: STORM_BSS_PIECE, the samples one workgroup of storm_bss_sdr_rows correlates
 LPC_TILE = 8                     # include/storm_hip.h: STORM_LPC_TILE, the consecutive frames one workgroup of storm_lpc_measures_rows takes
 RAMP_KINDS = {"hann": 0, "linear": 1}        # include/storm_hip.h: STORM_RAMP_HANN, STORM_RAMP_LINEAR
+ENSEMBLE_TILE = 1024             # include/storm_hip.h: STORM_ENSEMBLE_TILE, the consecutive bins one workgroup of storm_ensemble_combine_rows takes
+ENSEMBLE_MAX_DRAWS = 32          # include/storm_hip.h: STORM_ENSEMBLE_MAX_DRAWS
+ENSEMBLE_MODES = {"mean": 0, "mag_mean": 1, "mag_median": 2}     # include/storm_hip.h: STORM_ENSEMBLE_MEAN, _MAG_MEAN, _MAG_MEDIAN
 
 
 class StormError(RuntimeError):
@@ -168,6 +171,8 @@ _SIGNATURES = {
     "storm_lpc_measures_rows": ([_vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _vp, _i, _vp], C.c_int),
     "storm_crossfade_ramp": ([_i, _i, _vp], C.c_int),
     "storm_crossfade_rows": ([_vp, _i, _ll, _vp, _i, _ll, _ll, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp], C.c_int),
+    "storm_ensemble_scratch_bytes": ([_i, _i, _i, _i], C.c_longlong),
+    "storm_ensemble_combine_rows": ([_vp, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _vp, C.c_float, C.c_float, _i, _vp], C.c_int),
     "storm_xcorr_num_partials": ([_ll, _ll, _i], C.c_int),
     "storm_xcorr_lag_rows": ([_vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _ll, _ll, _vp, _vp, _i, _vp], C.c_int),
     "storm_shift_rows": ([_vp, _vp, _vp, _i, _ll, _ll, _ll, _vp, _i, _vp], C.c_int),

@@ -405,6 +405,113 @@ class _Base(nn.Module):
                     result[i] = dm.resample(result[i].contiguous(), dm.sample_rate, int(rates[i]))[:counts[i]]
         return (result, nfe) if return_nfe else result
 
+    # the sampler keywords enhance_batch names, with its defaults (StochasticRegenerationModel: its own)
+    _sampler_defaults = dict(sampler_type="pc", predictor="reverse_diffusion", corrector="ald", N=50, corrector_steps=1, snr=0.5)
+    _ENSEMBLE_COMBINES = ("mean", "mag_mean", "mag_median", "medoid")
+
+    def enhance_ensemble(self, y, draws=1, combine="mean", keys=None, seed=None, lengths=None, sr=None, batch=16, return_spread=False,
+                         return_stft=False, return_nfe=False, **sampler_kwargs):
+        """(ScoreModel and StochasticRegenerationModel.)  `draws` = K samples of the clean-speech posterior per utterance of y [B, L],
+        combined on the device (ops.ensemble_combine; the definition is in include/storm_hip.h) -> the combined waveforms fp32 [B, L].
+        The (utterance, draw) pairs form a pool in that order; every run of `batch` of them is ONE sampler run (K draws of one utterance
+        fill the batch that a single utterance leaves empty), draw k of utterance b with the Philox key ops.draw_key(key_b, k), so a draw
+        is what enhance_batch(y[b:b+1], row_seeds=[that key]) samples, whatever it is batched with.  The STFT, the peak (every draw of an
+        utterance is normalised by that utterance's peak) and - StoRM - the denoiser run once per utterance; after the last run ONE
+        combine launch forms, per bin of the LINEAR spectrogram,
+          combine='mean': the mean of the draws;  'mag_mean' / 'mag_median': the mean's phase with the mean / median of the draws' magnitudes;
+          'medoid': the draw closest to the mean over the whole utterance (its own spectrogram through the unchanged spec_to_wav: that
+          utterance's result is its chosen draw's own result, bit for bit; chosen and gathered on the device).
+        draws=1: no combine - enhance_batch(y, row_seeds=keys), bit for bit; the spread is zeros and the agreement +inf.
+        keys: one Philox key per utterance; seed=s: utterance i has the key s + i; neither: drawn from torch's generator.  lengths, sr: as
+        in enhance_batch.  sampler_kwargs: enhance_batch's (sampler_type, predictor, corrector, N, corrector_steps, snr, ...).
+        Returns the waveforms and, in this order: return_spread - the per-bin spread fp32 [B, F, T] (the draws' standard deviation around
+        their mean, padded frame count, zeros past an utterance's own frames) and the per-utterance agreement 10 log10(E / D) in dB, fp64
+        [B] (E the energy of the mean, D the draws' mean squared distance from it), both over the frames that reach the utterance's samples,
+        ceil((length + n_fft // 2) / hop) of them; return_stft - the combined linear spectrogram
+        complex64 [B, F, T]; return_nfe - the score evaluations of all (utterance, draw) rows, summed, as enhance_long counts
+        them (enhance_batch has one sampler run and returns that run's count; here there are several runs of different widths)."""
+        from . import ops
+        K = int(draws)
+        if K < 1 or K > ops.ENSEMBLE_MAX_DRAWS:
+            raise ValueError(f"draws={draws}: between 1 and {ops.ENSEMBLE_MAX_DRAWS}")
+        if combine not in self._ENSEMBLE_COMBINES:
+            raise ValueError(f"combine={combine!r}: one of {list(self._ENSEMBLE_COMBINES)}")
+        if int(batch) < 1:
+            raise ValueError(f"batch={batch}")
+        for name in ("row_seeds", "peak", "noise_fn", "z"):
+            if name in sampler_kwargs:
+                raise ValueError(f"enhance_ensemble forms {name} itself")
+        if keys is not None and seed is not None:
+            raise ValueError("keys and seed exclude each other")
+        if y.dim() != 2:
+            raise ValueError("expected a waveform batch [B, L]")
+        B = y.shape[0]
+        if keys is not None:
+            keys = [int(v) for v in keys]
+            if len(keys) != B:
+                raise ValueError(f"keys has {len(keys)} entries for {B} utterances")
+        elif seed is not None:
+            keys = [int(seed) + i for i in range(B)]
+        else:
+            keys = [int(v) for v in torch.randint(2 ** 62, (B,))]
+        if self._off_rate(sr):
+            y16, l16 = self._to_model_rate(y, sr, lengths)
+            res = self.enhance_ensemble(y16, K, combine, keys=keys, lengths=l16, batch=batch, return_spread=return_spread, return_stft=return_stft,
+                                        return_nfe=return_nfe, **sampler_kwargs)
+            res = res if isinstance(res, tuple) else (res,)
+            return self._ensemble_result((self._from_model_rate(res[0], sr, l16, lengths, y.shape[1]),) + res[1:])
+        dm = self.data_module
+        kw = {**self._sampler_defaults, **sampler_kwargs}
+        named = [kw.pop(k) for k in ("sampler_type", "predictor", "corrector", "N", "corrector_steps", "snr")]
+        with torch.no_grad():
+            Y, peak, T_orig = self._prepare(y, lengths)
+            F, Tp = Y.shape[2], Y.shape[3]
+            # (StoRM: the denoiser's output, once per utterance; one draw: the denoiser runs inside the one sampler run, as in enhance_batch)
+            cond = None if K == 1 else self._ensemble_condition(Y, int(batch), kw)
+            pairs = [(b, k) for b in range(B) for k in range(K)]
+            step = B if K == 1 else int(batch)                            # (one draw: the one sampler run of enhance_batch)
+            pool, nfe = [], 0
+            for j0 in range(0, len(pairs), step):
+                run = pairs[j0:j0 + step]
+                whole = [b for b, _ in run] == list(range(B))
+                idx = None if whole else torch.tensor([b for b, _ in run], device=Y.device)
+                sample, n_eval = self._sample_spec(Y if whole else Y.index_select(0, idx), *named, [ops.draw_key(keys[b], k) for b, k in run], dict(kw),
+                                                   **({} if cond is None else {"Y_denoised": cond if whole else cond.index_select(0, idx)}))
+                own = getattr(self, "last_nfev_rows", None)               # (ODE: every row's own count; otherwise all rows take n_eval)
+                nfe += sum(int(v) for v in own) if own else int(n_eval) * len(run)
+                pool.append(sample)
+            pool = pool[0] if len(pool) == 1 else torch.cat(pool, dim=0)
+            # the frames that reach an utterance's samples (frame t covers t hop +- n_fft // 2): the padding frames behind them are left out
+            own_frames = [min(Tp, -(-(int(n) + dm.n_fft // 2) // dm.hop_length)) for n in (lengths if lengths is not None else [T_orig] * B)]
+            if K == 1:
+                x_hat = dm.spec_to_wav(pool, T_orig, peak, lengths=lengths)
+                spread = torch.zeros((B, F, Tp), dtype=torch.float32, device=Y.device) if return_spread else None
+                agree = torch.full((B,), float("inf"), dtype=torch.float64, device=Y.device)
+                stft = dm.spec_back(pool[:, 0]) if return_stft else None
+            else:
+                table = torch.arange(B * K, dtype=torch.int32, device=Y.device).reshape(B, K)
+                stft, spread, rows, best = ops.ensemble_combine(pool[:, 0], table, dm.spec_factor, dm.spec_abs_exponent,
+                                                                mode="mean" if combine == "medoid" else combine, frames=own_frames,
+                                                                spread=return_spread)
+                agree = 10.0 * torch.log10(rows[:, 0] / rows[:, 1])
+                if combine == "medoid":
+                    chosen = pool.index_select(0, table.gather(1, best.long().unsqueeze(1)).reshape(-1).long())
+                    x_hat = dm.spec_to_wav(chosen, T_orig, peak, lengths=lengths)
+                    stft = dm.spec_back(chosen[:, 0]) if return_stft else None
+                else:
+                    x_hat = ops.istft(stft, int(T_orig), peak, n_fft=dm.n_fft, hop=dm.hop_length, spec_factor=1.0, spec_abs_exponent=1.0,
+                                      window=dm.window_type, lengths=lengths)
+        return self._ensemble_result((x_hat,) + ((spread, agree) if return_spread else ()) + ((stft,) if return_stft else ())
+                                     + ((nfe,) if return_nfe else ()))
+
+    @staticmethod
+    def _ensemble_result(res):
+        return res if len(res) > 1 else res[0]
+
+    def _ensemble_condition(self, Y, batch, kw):
+        """what every draw of an utterance shares besides Y (StochasticRegenerationModel: the denoiser's output); None: nothing"""
+        return None
+
     @staticmethod
     def _slice_keys(kwargs, sl):
         """the sampler keywords of the batch slice `sl`: per-row keys (row_seeds) go with their rows"""
@@ -493,6 +600,13 @@ class ScoreModel(_Base):
             x_hat = self._from_model_rate(x16, sr, l16, lengths, y.shape[1])
             return (x_hat, nfe) if return_nfe else x_hat
         Y, peak, T_orig = self._prepare(y, lengths, peak)
+        sample, nfe = self._sample_spec(Y, sampler_type, predictor, corrector, N, corrector_steps, snr, row_seeds, kwargs)
+        x_hat = self.data_module.spec_to_wav(sample, T_orig, peak, lengths=lengths)
+        return (x_hat, nfe) if return_nfe else x_hat
+
+    def _sample_spec(self, Y, sampler_type, predictor, corrector, N, corrector_steps, snr, row_seeds, kwargs):
+        """enhance_batch from the prepared spectrograms Y [B,1,F,Tpad] to the sampler's output: (sample, score evaluations).  kwargs: the
+        caller's remaining sampler keywords (a dict this method may add to)."""
         if row_seeds is not None:
             kwargs["row_seeds"] = row_seeds
         if sampler_type == "pc":
@@ -506,8 +620,7 @@ class ScoreModel(_Base):
             raise ValueError("{} is not a valid sampler type!".format(sampler_type))
         sample, nfe = sampler()
         self.last_nfev_rows = getattr(sampler, "nfev_rows", None)     # ODE: the evaluations every row needed on its own
-        x_hat = self.data_module.spec_to_wav(sample, T_orig, peak, lengths=lengths)
-        return (x_hat, nfe) if return_nfe else x_hat
+        return sample, nfe
 
     def validation_loss(self, x, y, t=None, z=None, seed=None, row_seeds=None, frames=None, reduce=True):
         """The reference's `_step` (model.py:138-154), the number it logs as valid_loss, on a spectrogram batch x (clean), y (noisy)
@@ -611,6 +724,16 @@ class DiscriminativeModel(ScoreModel):
                 X_hat = self._forward_transform(self._stft(X_hat.reshape(X_hat.shape[0], -1))).unsqueeze(1)
             x_hat = self.data_module.spec_to_wav(X_hat, T_orig, peak, lengths=lengths)
         return (x_hat, 1) if return_nfe else x_hat
+
+    def enhance_ensemble(self, y, draws=1, combine="mean", lengths=None, sr=None, return_spread=False, return_stft=False, return_nfe=False,
+                         **ignored_kwargs):
+        """A predictive model draws no noise: every draw would be the same output, so draws > 1 is refused.  draws=1: enhance_batch."""
+        if int(draws) != 1:
+            raise ValueError(f"DiscriminativeModel.enhance_ensemble: draws={draws} - a predictive model has no noise to draw from, its one "
+                             f"output is the only draw (draws=1)")
+        if return_spread or return_stft:
+            raise ValueError("DiscriminativeModel.enhance_ensemble: return_spread and return_stft belong to the sampling models")
+        return self.enhance_batch(y, lengths=lengths, sr=sr, return_nfe=return_nfe)
 
     def enhance(self, y, sr=None, **ignored_kwargs):
         """sr: y's sample rate when it is not 16 kHz - resampled on the device before and after, as in ScoreModel.enhance_batch"""
@@ -723,12 +846,27 @@ class StochasticRegenerationModel(_Base):
             x_hat = self._from_model_rate(out[0], sr, l16, lengths, y.shape[1])
             return (x_hat, out[1]) if return_nfe else x_hat
         Y, peak, T_orig = self._prepare(y, lengths, peak)
+        sample, nfe = self._sample_spec(Y, sampler_type, predictor, corrector, N, corrector_steps, snr, row_seeds, kwargs, denoiser_only=denoiser_only)
+        if return_stft:                                     # (model.py:766-767; a batch gets every row's normalisation factor)
+            norm = float(peak[0]) if sample.shape[0] == 1 else peak.detach().reshape(-1).cpu()
+            return sample.squeeze(), Y.squeeze(), T_orig, norm
+        x_hat = self.data_module.spec_to_wav(sample, T_orig, peak, lengths=lengths)
+        return (x_hat, nfe) if return_nfe else x_hat
+
+    _sampler_defaults = dict(sampler_type="pc", predictor="reverse_diffusion", corrector="none", N=30, corrector_steps=1, snr=0.5)
+
+    def _sample_spec(self, Y, sampler_type, predictor, corrector, N, corrector_steps, snr, row_seeds, kwargs, denoiser_only=False, Y_denoised=None):
+        """enhance_batch from the prepared spectrograms Y [B,1,F,Tpad] to the sampler's output: (sample, score evaluations).  kwargs: the
+        caller's remaining sampler keywords (a dict this method may add to).  Y_denoised: the denoiser's output for these rows where the
+        caller already has it (enhance_ensemble: once per utterance, replicated for its draws); None: forward_denoiser(Y)."""
+        denoiser_only = bool(kwargs.pop("denoiser_only", denoiser_only))
         kwargs.setdefault("langevin_per_row", True)
         if row_seeds is not None:
             kwargs["row_seeds"] = row_seeds
         nfe = 0
         with torch.no_grad():
-            Y_denoised = self.forward_denoiser(Y) if self.denoiser_net is not None else None
+            if Y_denoised is None:
+                Y_denoised = self.forward_denoiser(Y) if self.denoiser_net is not None else None
             if self.score_net is not None and not denoiser_only:
                 score_conditioning = self._score_conditioning(Y, Y_denoised)
                 if sampler_type != "pc":
@@ -739,11 +877,14 @@ class StochasticRegenerationModel(_Base):
                 sample, nfe = sampler()
             else:
                 sample = Y_denoised
-        if return_stft:                                     # (model.py:766-767; a batch gets every row's normalisation factor)
-            norm = float(peak[0]) if sample.shape[0] == 1 else peak.detach().reshape(-1).cpu()
-            return sample.squeeze(), Y.squeeze(), T_orig, norm
-        x_hat = self.data_module.spec_to_wav(sample, T_orig, peak, lengths=lengths)
-        return (x_hat, nfe) if return_nfe else x_hat
+        return sample, nfe
+
+    def _ensemble_condition(self, Y, batch, kw):
+        if self.denoiser_net is None:
+            return None
+        if Y.shape[0] <= batch:
+            return self.forward_denoiser(Y)                               # ONE evaluation for all utterances, none per draw
+        return torch.cat([self.forward_denoiser(Y[j0:j0 + batch]) for j0 in range(0, Y.shape[0], batch)], dim=0)
 
     def enhance(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="none", N=30, corrector_steps=1,
                 snr=0.5, timeit=False, scale_factor=None, return_stft=False, denoiser_only=False, sr=None, **kwargs):

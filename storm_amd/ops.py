@@ -912,6 +912,69 @@ def crossfade_rows(pool, win_row, rec_len, rec_windows, W, V, ramp=None, width=N
     return out
 
 
+# ---------------------------------------------------------------- posterior ensembles -----
+ENSEMBLE_TILE = L.ENSEMBLE_TILE          # consecutive bins per workgroup of storm_ensemble_combine_rows (tests place bin counts around it)
+ENSEMBLE_MAX_DRAWS = L.ENSEMBLE_MAX_DRAWS
+ENSEMBLE_MODES = tuple(L.ENSEMBLE_MODES)                  # "mean", "mag_mean", "mag_median"
+DRAW_KEY_STEP = 0xD1B54A32D192ED03       # draw k > 0 of an utterance draws from key + k * this, mod 2^63
+
+
+def draw_key(key, k):
+    """the Philox key of draw k of an utterance with key `key`: the key itself for k = 0 (the single draw of before), else
+    (key + k * 0xD1B54A32D192ED03) mod 2^63"""
+    key, k = int(key), int(k)
+    if k < 0:
+        raise ValueError(f"draw_key: k={k}")
+    return key if k == 0 else (key + k * DRAW_KEY_STEP) % 2 ** 63
+
+
+def ensemble_combine(pool, draw_row, factor, exponent, mode="mean", frames=None, spread=False):
+    """K draws per utterance combined in ONE launch pair (storm_ensemble_combine_rows; the definition is in include/storm_hip.h).
+    pool: sampler outputs in the model's transformed domain, complex64 [N, F, T] (bins contiguous; the row stride may exceed F T);
+    draw_row: [B][K] pool rows, host ints or a device int32 tensor [B, K] (draw k of utterance b; any order); factor, exponent: the data
+    module's spec_factor and spec_abs_exponent; mode: one of ENSEMBLE_MODES; frames: per-utterance valid frame counts (bins past them are
+    not read and come back as zeros).  Returns (out complex64 [B, F, T] in the LINEAR STFT domain, spread fp32 [B, F, T] or None,
+    rows fp64 [B, 2 + K] = (E, D, d_0 .. d_{K-1}), best int32 [B] = the medoid draw)."""
+    if pool.dim() != 3 or pool.dtype != torch.complex64 or min(pool.shape) < 1:
+        raise ValueError(f"ensemble_combine: pool is {pool.dtype} {tuple(pool.shape)}, expected complex64 [N, F, T]")
+    if mode not in L.ENSEMBLE_MODES:
+        raise ValueError(f"ensemble_combine: mode {mode!r}: one of {list(ENSEMBLE_MODES)}")
+    N, F, T = pool.shape
+    if pool.stride(2) != 1 or pool.stride(1) != T or (N > 1 and pool.stride(0) < F * T):
+        pool = pool.contiguous()
+    if pool.data_ptr() % 16:
+        pool = pool.clone(memory_format=torch.contiguous_format)               # (a view that starts off a 16-byte boundary: the library refuses it)
+    stride = pool.stride(0) if N > 1 else F * T                  # (a one-row tensor's row stride is whatever its producer left there)
+    if isinstance(draw_row, torch.Tensor):
+        if draw_row.dim() != 2:
+            raise ValueError(f"ensemble_combine: draw_row is {tuple(draw_row.shape)}, expected [B, K]")
+        table = draw_row.to(device=pool.device, dtype=torch.int32).contiguous()
+    else:
+        rows = [[int(v) for v in r] for r in draw_row]
+        if not rows or any(len(r) != len(rows[0]) for r in rows):
+            raise ValueError("ensemble_combine: draw_row must be [B][K] with one K for every utterance")
+        if any(v < 0 or v >= N for r in rows for v in r):
+            raise ValueError(f"ensemble_combine: draw_row names a row outside the pool of {N} rows")
+        table = torch.tensor(rows, dtype=torch.int32).reshape(len(rows), len(rows[0])).to(pool.device)
+    B, K = table.shape
+    if B < 1 or K < 1 or K > ENSEMBLE_MAX_DRAWS:
+        raise ValueError(f"ensemble_combine: draw_row is [{B}, {K}]: at least one utterance and 1 <= K <= {ENSEMBLE_MAX_DRAWS} draws")
+    _metric_lengths("ensemble_combine", frames, B, T, "frames")
+    out = torch.empty((B, F, T), dtype=torch.complex64, device=pool.device)
+    sp = torch.empty((B, F, T), dtype=torch.float32, device=pool.device) if spread else None
+    rows_out = _alloc((B, 2 + K), torch.float64, pool)
+    best = _alloc((B,), torch.int32, pool)
+    ws = torch.empty((max(L.lib().storm_ensemble_scratch_bytes(B, F, T, K) // 8, 1),), dtype=torch.float64, device=pool.device)
+    fr = _row_len(frames, pool)
+    if not L.is_sim() and not pool.is_cuda:
+        raise L.StormError("storm_amd ops run on the GPU only: got a CPU tensor (there is no CPU fallback)")
+    L.check(L.lib().storm_ensemble_combine_rows(pool.data_ptr(), N, stride, L.ptr(table),
+                                                L.ptr(_r(out)), L.ptr(sp), L.ptr(rows_out), L.ptr(best), L.ptr(ws), 8 * ws.numel(), B, K, F, T,
+                                                L.ptr(fr), float(factor), float(exponent), L.ENSEMBLE_MODES[mode], L.stream()),
+            "storm_ensemble_combine_rows")
+    return out, sp, rows_out, best
+
+
 # ---------------------------------------------------------------- metrics -----------------
 METRICS_CHUNK = L.METRICS_CHUNK          # samples per workgroup of storm_energy_ratios_rows (tests place lengths around it)
 

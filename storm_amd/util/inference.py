@@ -79,7 +79,7 @@ def score_batch(clean, noisy, estimate, lengths=None, stoi=False, fs=16000, alig
 
 
 def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminative=False, pairs=None, batch=16, noise_for=None,
-                   metrics=False, estoi=None, lpc=False, **enhance_kwargs):
+                   metrics=False, estoi=None, lpc=False, draws=1, combine="mean", **enhance_kwargs):
     """Returns (pesq, si_sdr, estoi, [noisy, estimate, clean spectrograms] | None, [noisy, estimate, clean audio] | None),
     the reference's tuple.  `discriminative` is accepted for signature parity (the model class decides the path).
     noise_for(ids) -> noise_fn: injected sampler noise for the micro-batch of files `ids` (parity tests; production runs
@@ -87,7 +87,13 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
     numbers, {si_sdr, si_sir, si_sar, lsd, isnr} as floats, computed on the same micro-batches.
     estoi="device": the third element is the mean over the files of the device ESTOI (ops.stoi_rows at 16 kHz, one call per micro-batch),
     whether or not pystoi imports, and the sixth element gains the means stoi and estoi; None: pystoi on the host, NaN without it.
-    lpc=True (with metrics=True): the sixth element gains the means seg_snr, llr and cd of score_batch(lpc=True) at 16 kHz."""
+    lpc=True (with metrics=True): the sixth element gains the means seg_snr, llr and cd of score_batch(lpc=True) at 16 kHz.
+    draws=K > 1, combine: every file's estimate is model.enhance_ensemble's (K draws per file combined on the device; its keys come from
+    seed=s - file i has the key s + i - or keys=, one per file in the files' order, among the keywords, or are drawn); draws=1 changes nothing."""
+    if int(draws) < 1:
+        raise ValueError(f"draws={draws}: at least 1")
+    if int(draws) > 1 and noise_for is not None:
+        raise ValueError("draws > 1 draws its noise in the kernels from per-draw keys: noise_for does not apply")
     if estoi not in (None, "device"):
         raise ValueError(f"estoi={estoi!r}: None (pystoi on the host) or 'device'")
     model.eval()
@@ -116,7 +122,14 @@ def evaluate_model(model, num_eval_files, spec=False, audio=False, discriminativ
         kw = dict(enhance_kwargs)
         if noise_for is not None:
             kw["noise_fn"] = noise_for(ids)
-        if batched:
+        if int(draws) > 1:
+            if kw.get("seed") is not None:                                  # a file's key follows its index, not its place in a micro-batch
+                first = int(kw.pop("seed"))
+                kw["keys"] = [first + i for i in ids]
+            elif kw.get("keys") is not None:                                # keys=: one per file, in the files' order
+                kw["keys"] = [int(kw["keys"][i]) for i in ids]
+            x_hat = model.enhance_ensemble(y, draws=int(draws), combine=combine, lengths=lens if len(set(lens)) > 1 else None, batch=batch, **kw)
+        elif batched:
             x_hat = model.enhance_batch(y, lengths=lens if len(set(lens)) > 1 else None, **kw)
         else:
             x_hat = model.enhance(y[:1], **kw).reshape(1, -1)         # (N / snr / corrector_steps ... reach the model here too: util/inference.py:49)
